@@ -25,14 +25,20 @@ N > 1: the same file; the Lanczos rows are sharded (strong scaling of the
 sharded phase), the KL loop stays on rank 0.  `--gpus N` without WORLD_SIZE
 starts the N ranks itself (torch.distributed.run, before any GPU call).
 
-Also reported: `roofline` of the Lanczos SpMV (HIP kernel timestamps of the
+A plain run does only what `value` needs: set-up, warm-up, the timed steps,
+the result line.  `--dump-outputs DIR` also writes what the last timed step
+returned (dump_outputs below) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
+
+With `--full`, also reported: `roofline` of the Lanczos SpMV (HIP kernel timestamps of the
 SpMVs of the timed steps; SURVEY §8d algorithmic bytes; PMC traffic from
 rocprofv3 passes over a resident solve run as child processes before the
 GPU is touched here), `cpu_baseline` (the oracle restatement on this host's
 cores, 1 core and all cores, whole solve of the headline workload to
 convergence, swap log compared), per-config sub-results (ibm01, ibm10, the
 whole 1.0x and 2.0x synthetics), the resident-input solve time and the syn10
-sharded Lanczos phase.
+sharded Lanczos phase, and `parity` (the last timed step against the committed
+reference fixture).  Without `--full` those keys are null.
 """
 import argparse
 import csv
@@ -172,6 +178,34 @@ def headline_parity(ctx, path, out_dir, n, last, is_headline):
             "reference": "tests/golden/syn115_lcc: real cKL (built from cKL.cpp) run on the converged Fiedler split"}
 
 
+def dump_outputs(d, ctx, last, swap_log, results_file):
+    """What a caller of the timed path receives from its last step, as
+    <d>/<name>.npy (float32 where the library computes in fp32, else float64;
+    under 4 MB at the headline size; a larger workload's arrays are sampled, see save):
+      swap_log      (swaps, 7)  iter, node_left, node_right, max_gain, min_gain, gain, cut
+      split         (nodes,)    side of every node after the device's median split
+      results_file  (rows, 3)   the results file's rows: iteration, cut, gain
+      scalars       (8,)        lambda1, median, KL iterations, initial cut, best cut,
+                                best iteration, net cut of the best prefix, final net cut"""
+    os.makedirs(d, exist_ok=True)
+
+    def save(name, a):  # 16 MB an array (64 MB in all): past that, a fixed seeded sample of its rows, in order
+        rows = max(1, (16 << 20) // max(1, a[:1].nbytes))
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), rows, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+    ints = np.stack([swap_log[f].astype(np.float64) for f in ("iter", "node_left", "node_right")], axis=1)
+    f32 = np.stack([swap_log[f] for f in ("max_gain", "min_gain", "gain", "cut")], axis=1)
+    save("swap_log", np.concatenate([ints, f32.astype(np.float64)], axis=1))
+    save("split", ctx.kl_sides(0).astype(np.float32))
+    save("results_file", np.loadtxt(results_file, dtype=np.float64, ndmin=2))
+    kl = last["kl"]
+    save("scalars", np.array(
+        [last["lambda"], last["median"], kl["iterations"], kl["initial_cut"], kl["best_cut"], kl["best_iter"],
+         kl["net_cut_best"], kl["net_cut_final"]], dtype=np.float64))
+
+
 def cpu_baseline(hgr, split_npz, threads, max_matvec):
     """oracle/cpu_baseline.py in a child process (CPU only), pinned to `threads` cores;
     its progress lines go straight to this process's stderr."""
@@ -231,12 +265,19 @@ def main():
                     help="lcc: the synthetic's largest connected component (default); full: the whole synthetic")
     ap.add_argument("--comm", choices=["auto", "rccl", "host"], default="auto",
                     help="multi-rank exchange: RCCL over xGMI, or host-staged (several ranks per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: roofline and rocprofv3 passes, parity "
+                         "with the reference fixture, CPU baseline, sub-configs, resident solve, syn10, fresh process")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip sub-configs, sweep, PMC and syn10 legs")
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--prof-dir", default=None,
                     help="keep the rocprofv3 passes' CSVs here (default: a temporary directory)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU, started before any GPU call or package import
@@ -253,7 +294,7 @@ def main():
     if args.prof_dir:
         work = os.path.join(os.path.abspath(args.prof_dir), f"rank{rank}")
         os.makedirs(work, exist_ok=True)
-    extras = not args.no_extras and world == 1
+    extras = args.full and not args.no_extras and world == 1
 
     # rocprofv3 passes first: child processes, before this process touches the GPU
     #  * kernel trace of the bench's own step (1 untimed + 3 solve_file steps):
@@ -263,7 +304,7 @@ def main():
     prof = {}
     lcc = args.workload == "lcc"
     wl = f"{args.mult:g}lcc" if lcc else f"{args.mult:g}"  # tools/spmv_probe.py's workload argument
-    if world > 1 and rank == 0 and not args.no_extras and not args.no_pmc:
+    if args.full and world > 1 and rank == 0 and not args.no_extras and not args.no_pmc:
         # the sharded SpMV (syn10 at this N): rank 0's rows, one process with
         # no collective, while the other ranks wait in the rendezvous below
         t = time.time()
@@ -284,8 +325,8 @@ def main():
             {k: (v if not k.startswith("trace") else {n[:40]: c for n, c in list((v or {}).items())[:6]})
              for k, v in prof.items()}))
 
-    import torch.distributed as dist
     if world > 1:
+        import torch.distributed as dist
         # gloo prints its peer connections on fd 1: rank 0's stdout must carry
         # the JSON line alone, so fd 1 points at stderr while it connects
         sys.stdout.flush()
@@ -365,28 +406,13 @@ def main():
     elapsed = max_over_ranks(time.time() - t0)
     sec_per_step = elapsed / args.steps
     last, swap_log = results[-1]
-    # the SpMV's kernel timestamps come from one more step, untimed: the timed
-    # steps launch without timing events (a launch with events costs the host
-    # ~7 us more, tools/lanczos_wall.py).  (The timed steps replay the
-    # Lanczos chunks' HIP graphs on one context; a step with events launches
-    # eagerly.)
-    ev_step = step(time_spmv=True)
-    barrier()
     log(f"timed: {args.steps} steps, {sec_per_step * 1e3:.2f} ms/step; last step {last['t_total']:.4f} s "
         f"(lanczos {last['t_lanczos']:.4f}, kl {last['t_kl']:.4f}, {last['lanczos']['matvecs']} matvecs, "
         f"{last['kl']['iterations']} swaps)")
-    parity = None
-    if rank == 0:
-        parity = headline_parity(ctx, path, out_dir, n, last, lcc and args.mult == 1.15 and args.seed == 1)
-        log(f"parity: {parity}")
-    # the gather-only ceiling of the step's own SpMV (same grid, matrix stream
-    # and x gathers, nothing else; ek_spmv_gather_bench), and the product
-    # kernel back to back on the same matrix, for the roofline's reading
-    ceil_us = ctx.spmv_gather_bench(200)
-    prod_bb_us = ctx.spmv_bench(200, fused=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(os.path.abspath(args.dump_outputs), ctx, last, swap_log,
+                     os.path.join(out_dir, "results", os.path.basename(path) + "_KL_CutSize_EIG_output.txt"))
     lz = [r[0]["lanczos"] for r in results]
-    spmv_timed = ev_step[0]["lanczos"]["spmv_timed"]
-    spmv_us = 1e3 * ev_step[0]["lanczos"]["spmv_ms"] / max(1, spmv_timed)
     comm_ms = sum(x["comm_ms"] for x in lz) / len(lz)
     phases = {k: round(float(np.median([r[0][k] for r in results])), 4) for k in
               ("t_read", "t_laplacian", "t_spmv_setup", "t_lanczos", "t_split", "t_kl_graph_wait", "t_kl_setup",
@@ -398,11 +424,91 @@ def main():
     off = ek.shard_map(h, world)  # the nnz-balanced map ek_solve_file's device build used
     row0, nrows = int(off[rank]), int(off[rank + 1] - off[rank])
     alg_bytes = ctx.spmv_bytes(fused=False)  # 12 nnz + 4(nrows+1) + 8n (x) + 8 nrows (y)
+    nnz_local = int((alg_bytes - 4 * (nrows + 1) - 8 * n - 8 * nrows) // 12)
+
+    def finish():
+        ctx.close()
+        if not args.prof_dir:
+            shutil.rmtree(work, ignore_errors=True)
+        if world > 1:
+            dist.destroy_process_group()
+
+    # the result line: what the timed steps alone give; the --full legs fill in the rest
+    out = {
+        "metric": "wall-clock to final cut (s) + cut size, ibm18.hgr; SpMV GB/s vs HBM peak",
+        "value": round(sec_per_step, 6),
+        "unit": "s",
+        "value_is": ("the warm-context step: one in-process .hgr file -> results file solve (ek_solve_file) with the "
+                     "GPU context up, as a service runs it; e2e_s is the metric as SURVEY §8d states it"),
+        "e2e_s": None,
+        "e2e_is": ("process start -> results written: `gKL2 <headline .hgr> -EIG` spawned fresh (HIP start-up, library "
+                   "load, parse, solve, write), median of 5 (e2e_fresh_breakdown)"),
+        "cut": last["kl"]["net_cut_best"],
+        "cut_is": ("integer net cut of the best KL prefix (nets with pins on both sides), cKL.cpp:392-403's split; "
+                   "the fp32 running cut is result.best_cut"),
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(sec_per_step * 1e3, 4),
+        "higher_is_better": False,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64 (Lanczos) + f32 (KL gains, bit-exact with cKL)",
+        "data": "synthetic (seeded ISPD98-shaped generator written to .hgr; ibm18.hgr not shipped)",
+        "full": args.full,
+        "config": {"workload": (f"ibm18-size connected synthetic: largest component of the {args.mult:g}x seed-"
+                                f"{args.seed} generator output, .hgr file -> results file" if lcc else
+                                f"ibm18-shape synthetic {args.mult:g}x seed {args.seed}: .hgr file -> results file"),
+                   "nodes": n, "nets": nets, "pins": npins, "laplacian_nnz": nnz_local if world == 1 else None,
+                   "parallelism": f"lanczos row-shard x{world} ({comm if world > 1 else 'single'}), KL 1 GPU"},
+        "roofline": None,
+        "cpu_baseline": None,
+        "parity": None,
+        "result": {"lambda1": last["lambda"], "lanczos_matvecs": last["lanczos"]["matvecs"],
+                   "lanczos_restarts": last["lanczos"]["restarts"], "residual": last["lanczos"]["residual"],
+                   "kl_iterations": last["kl"]["iterations"], "kl_loop_ms": round(last["kl"]["loop_ms"], 3),
+                   "initial_cut": last["kl"]["initial_cut"], "best_cut": last["kl"]["best_cut"],
+                   "net_cut_best": last["kl"]["net_cut_best"], "net_cut_final": last["kl"]["net_cut_final"],
+                   "best_iter": last["kl"]["best_iter"], "phases_median_s": phases, "phases_slowest_step_s": phases_worst,
+                   "step_walls_s": [round(w, 4) for w in step_walls],
+                   "step_totals_s": [round(r[0]["t_total"], 4) for r in results],
+                   "comm_ms_per_step": round(comm_ms, 3), "spmv_us_max_rank": None,
+                   "resident_solve": None},
+        "e2e_fresh_process_s": None,
+        "e2e_fresh_breakdown": None,
+        "configs": {},
+        "syn10_sharded_lanczos": None,
+        "stray_processes_reaped": None,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        finish()
+        return
+
+    # ---------------- --full: every other leg
+    # the SpMV's kernel timestamps come from one more step, untimed: the timed
+    # steps launch without timing events (a launch with events costs the host
+    # ~7 us more, tools/lanczos_wall.py).  (The timed steps replay the
+    # Lanczos chunks' HIP graphs on one context; a step with events launches
+    # eagerly.)
+    ev_step = step(time_spmv=True)
+    barrier()
+    parity = None
+    if rank == 0:
+        parity = headline_parity(ctx, path, out_dir, n, last, lcc and args.mult == 1.15 and args.seed == 1)
+        log(f"parity: {parity}")
+    # the gather-only ceiling of the step's own SpMV (same grid, matrix stream
+    # and x gathers, nothing else; ek_spmv_gather_bench), and the product
+    # kernel back to back on the same matrix, for the roofline's reading
+    ceil_us = ctx.spmv_gather_bench(200)
+    prod_bb_us = ctx.spmv_bench(200, fused=False)
+    spmv_timed = ev_step[0]["lanczos"]["spmv_timed"]
+    spmv_us = 1e3 * ev_step[0]["lanczos"]["spmv_ms"] / max(1, spmv_timed)
     fused_bytes = ctx.spmv_bytes(fused=True)  # + the fused epilogue's f read and basis-column write
     packed, stored = ctx.spmv_format(fused=True)
     # the same for every rank: every rank's SpMV is timed; report rank 0's and the max
     spmv_us_max = max_over_ranks(spmv_us)
-    nnz_local = int((alg_bytes - 4 * (nrows + 1) - 8 * n - 8 * nrows) // 12)
 
     # ---------------- resident-input solve (inputs already in HBM): the solve alone
     L_rows = None
@@ -526,9 +632,7 @@ def main():
         del h10
 
     if rank != 0:
-        ctx.close()
-        if world > 1:
-            dist.destroy_process_group()
+        finish()
         return
 
     # ---------------- sub-configs (N = 1): the file path on other inputs
@@ -695,57 +799,12 @@ def main():
             source="rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE passes over tools/spmv_probe.py resident in this run")
 
     strays = reap_strays()
-    out = {
-        "metric": "wall-clock to final cut (s) + cut size, ibm18.hgr; SpMV GB/s vs HBM peak",
-        "value": round(sec_per_step, 6),
-        "unit": "s",
-        "value_is": ("the warm-context step: one in-process .hgr file -> results file solve (ek_solve_file) with the "
-                     "GPU context up, as a service runs it; e2e_s is the metric as SURVEY §8d states it"),
-        "e2e_s": fresh,
-        "e2e_is": ("process start -> results written: `gKL2 <headline .hgr> -EIG` spawned fresh (HIP start-up, library "
-                   "load, parse, solve, write), median of 5 (e2e_fresh_breakdown)"),
-        "cut": last["kl"]["net_cut_best"],
-        "cut_is": ("integer net cut of the best KL prefix (nets with pins on both sides), cKL.cpp:392-403's split; "
-                   "the fp32 running cut is result.best_cut"),
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(sec_per_step * 1e3, 4),
-        "higher_is_better": False,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64 (Lanczos) + f32 (KL gains, bit-exact with cKL)",
-        "data": "synthetic (seeded ISPD98-shaped generator written to .hgr; ibm18.hgr not shipped)",
-        "config": {"workload": (f"ibm18-size connected synthetic: largest component of the {args.mult:g}x seed-"
-                                f"{args.seed} generator output, .hgr file -> results file" if lcc else
-                                f"ibm18-shape synthetic {args.mult:g}x seed {args.seed}: .hgr file -> results file"),
-                   "nodes": n, "nets": nets, "pins": npins, "laplacian_nnz": nnz_local if world == 1 else None,
-                   "parallelism": f"lanczos row-shard x{world} ({comm if world > 1 else 'single'}), KL 1 GPU"},
-        "roofline": roof,
-        "cpu_baseline": cpu,
-        "parity": parity,
-        "result": {"lambda1": last["lambda"], "lanczos_matvecs": last["lanczos"]["matvecs"],
-                   "lanczos_restarts": last["lanczos"]["restarts"], "residual": last["lanczos"]["residual"],
-                   "kl_iterations": last["kl"]["iterations"], "kl_loop_ms": round(last["kl"]["loop_ms"], 3),
-                   "initial_cut": last["kl"]["initial_cut"], "best_cut": last["kl"]["best_cut"],
-                   "net_cut_best": last["kl"]["net_cut_best"], "net_cut_final": last["kl"]["net_cut_final"],
-                   "best_iter": last["kl"]["best_iter"], "phases_median_s": phases, "phases_slowest_step_s": phases_worst,
-                   "step_walls_s": [round(w, 4) for w in step_walls],
-                   "step_totals_s": [round(r[0]["t_total"], 4) for r in results],
-                   "comm_ms_per_step": round(comm_ms, 3), "spmv_us_max_rank": round(spmv_us_max, 3),
-                   "resident_solve": resident},
-        "e2e_fresh_process_s": fresh,
-        "e2e_fresh_breakdown": fresh_breakdown,
-        "configs": subs,
-        "syn10_sharded_lanczos": syn10,
-        "stray_processes_reaped": strays,
-    }
+    out.update({"e2e_s": fresh, "roofline": roof, "cpu_baseline": cpu, "parity": parity,
+                "e2e_fresh_process_s": fresh, "e2e_fresh_breakdown": fresh_breakdown, "configs": subs,
+                "syn10_sharded_lanczos": syn10, "stray_processes_reaped": strays})
+    out["result"].update({"spmv_us_max_rank": round(spmv_us_max, 3), "resident_solve": resident})
     print(json.dumps(out), flush=True)
-    ctx.close()
-    if not args.prof_dir:
-        shutil.rmtree(work, ignore_errors=True)
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
     try:  # last word on descendants, after the context and the process group are gone
         import psutil
         kids = [(p.pid, " ".join(p.cmdline())[:120]) for p in psutil.Process().children(recursive=True)]

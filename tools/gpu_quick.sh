@@ -13,7 +13,7 @@ rc=$?
 grep -E "PASS|FAIL|ERROR|passed|failed" "$OUT/${TAG}_tests.log" | tail -40
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc $rc: stopping"; exit $rc; fi
 [ $rc -ne 0 ] && exit 1
-timeout -k 10 600 python -u bench.py --no-extras "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+timeout -k 10 600 python -u bench.py --full --no-extras "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 brc=$?
 tail -5 "$OUT/${TAG}_bench.err"
 python3 -c "
