@@ -86,6 +86,24 @@ class SolveResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _SOLVE_TIMES])
 
 
+KWAY_LEVELS = 8  # eigkl.h EK_KWAY_LEVELS
+
+
+class KwayOpts(_AbiStruct):
+    _fields_ = [("k", _I32), ("min_spectral", _I32), ("limit", _I32), ("write_results", _I32),
+                ("out_dir", ctypes.c_char_p), ("lanczos", LanczosOpts)]
+
+
+_KWAY_TIMES = ("t_induce", "t_lanczos", "t_kl", "t_metrics", "t_total")
+
+
+class KwayResult(_AbiStruct):
+    _fields_ = ([("k", _I32), ("bisections", _I32), ("fallback_splits", _I32), ("pad", _I32),
+                 ("part_min", _I64), ("part_max", _I64), ("cut_nets", _I64), ("connectivity", _I64),
+                 ("soed", _I64), ("matvecs", _I64), ("kl_swaps", _I64)]
+                + [(k, ctypes.c_double) for k in _KWAY_TIMES] + [("t_level", ctypes.c_double * KWAY_LEVELS)])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -173,6 +191,17 @@ _sig("ek_kl_set_partition_fiedler", ctypes.c_int, _P, _P, _P, _P)
 _sig("ek_kl_run", ctypes.c_int, _P, _I32, _P, _I64, ctypes.POINTER(KLResult))
 _sig("ek_kl_sides", ctypes.c_int, _P, _I32, _P)
 _sig("ek_cli_main", ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p))
+_sig("ek_kway_plan", ctypes.c_int, _I64, _I32, _P)
+_sig("ek_rank_split", ctypes.c_int, _I64, _P, _I64, _P)
+_sig("ek_hgr_induce", ctypes.c_int, _P, _P, ctypes.POINTER(_P), _P)
+_sig("ek_kway_metrics_host", ctypes.c_int, _I64, _P, _P, _P, _I32, _P)
+_sig("ek_rank_split_device", ctypes.c_int, _P, _I64, _P, _I64, _P)
+_sig("ek_kl_set_partition_fiedler_rank", ctypes.c_int, _P, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64))
+_sig("ek_kway_metrics", ctypes.c_int, _P, _I64, _P, _P, _P, _I32, _P)
+_sig("ek_kway_default_opts", None, ctypes.POINTER(KwayOpts))
+_sig("ek_partition_kway", ctypes.c_int, _P, _P, ctypes.POINTER(KwayOpts), _P, ctypes.POINTER(KwayResult))
+_sig("ek_partition_kway_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayOpts), _P,
+     ctypes.POINTER(KwayResult))
 
 lib = _lib
 
@@ -286,6 +315,17 @@ class Hypergraph:
         _chk(_lib.ek_hgr_largest_component(self._h, ctypes.byref(c), _p(m)), "largest_component")
         return Hypergraph(c), m
 
+    def induce(self, keep):
+        """(sub-hypergraph on the nodes with keep != 0, node map old -> new or -1): nets restricted to their
+        kept pins, those left with fewer than 2 dropped (ek_hgr_induce)."""
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+        if len(keep) != self.nodes:
+            raise ValueError(f"keep has {len(keep)} entries for {self.nodes} nodes")
+        c = _P()
+        m = np.empty(self.nodes, np.int32)
+        _chk(_lib.ek_hgr_induce(self._h, _p(keep), ctypes.byref(c), _p(m)), "induce")
+        return Hypergraph(c), m
+
     def laplacian(self):
         """fp64 clique Laplacian (cEIG.cpp:86-133)."""
         c = _P()
@@ -329,6 +369,50 @@ def median_split(v):
     bits = np.empty(len(v), np.uint8)
     _chk(_lib.ek_median_split(len(v), _p(v), ctypes.byref(med), _p(bits)), "median_split")
     return med.value, bits
+
+
+def kway_plan(n, k):
+    """Part sizes of the k-way recursion (ek_kway_plan): each floor(n/k) or ceil(n/k)."""
+    sizes = np.zeros(max(int(k), 1), np.int64)
+    _chk(_lib.ek_kway_plan(int(n), int(k), _p(sizes)), "kway_plan")
+    return sizes
+
+
+def rank_split(v, n1):
+    """bits = 1 for the n1 nodes smallest in (radix order of v, node id) (ek_rank_split)."""
+    v = np.ascontiguousarray(v, np.float64)
+    bits = np.empty(len(v), np.uint8)
+    _chk(_lib.ek_rank_split(len(v), _p(v), int(n1), _p(bits)), "rank_split")
+    return bits
+
+
+def kway_metrics_host(net_ptr, pins, part, k):
+    """(cut nets, connectivity, SOED) of a part vector, on the host (ek_kway_metrics_host)."""
+    net_ptr = np.ascontiguousarray(net_ptr, np.int64)
+    pins = np.ascontiguousarray(pins, np.int32)
+    part = np.ascontiguousarray(part, np.int32)
+    if len(pins) and int(pins.max()) >= len(part):
+        raise ValueError("part is shorter than the pins' node range")
+    out = np.zeros(3, np.int64)
+    _chk(_lib.ek_kway_metrics_host(len(net_ptr) - 1, _p(net_ptr), _p(pins), _p(part), int(k), _p(out)),
+         "kway_metrics_host")
+    return tuple(int(x) for x in out)
+
+
+def _kway_opts(k, min_spectral, limit, write_results, out_dir, lanczos):
+    o = KwayOpts()
+    _lib.ek_kway_default_opts(ctypes.byref(o))
+    o.k, o.min_spectral, o.limit, o.write_results = int(k), int(min_spectral), int(limit), 1 if write_results else 0
+    o.out_dir = os.fsencode(out_dir) if out_dir else None
+    for name, val in (lanczos or {}).items():
+        setattr(o.lanczos, name, val)
+    return o
+
+
+def _kway_result(r):
+    out = {k: getattr(r, k) for k, _ in KwayResult._fields_ if k not in ("pad", "t_level")}
+    out["t_level"] = list(r.t_level)
+    return out
 
 
 def eig_write(path, lam, median, bits, v):
@@ -557,6 +641,55 @@ class Context:
              "kl_set_partition_fiedler")
         self._n01 = (n0.value, n1.value)
         return med.value, n0.value, n1.value
+
+    def kl_set_partition_fiedler_rank(self, n1):
+        """kl_set_partition_fiedler with the rank split: side 1 gets the n1 nodes rank_split marks in the
+        Fiedler vector left on this context (ek_kl_set_partition_fiedler_rank).  Returns (n0, n1)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        _chk(_lib.ek_kl_set_partition_fiedler_rank(self._c, int(n1), ctypes.byref(a), ctypes.byref(b)),
+             "kl_set_partition_fiedler_rank")
+        self._n01 = (a.value, b.value)
+        return a.value, b.value
+
+    def rank_split_device(self, v, n1):
+        """rank_split run by the device kernels on an uploaded copy of v (ek_rank_split_device)."""
+        v = np.ascontiguousarray(v, np.float64)
+        bits = np.empty(len(v), np.uint8)
+        _chk(_lib.ek_rank_split_device(self._c, len(v), _p(v), int(n1), _p(bits)), "rank_split_device")
+        return bits
+
+    def kway_metrics(self, net_ptr, pins, part, k):
+        """(cut nets, connectivity, SOED) of a part vector, on the GPU (ek_kway_metrics)."""
+        net_ptr = np.ascontiguousarray(net_ptr, np.int64)
+        pins = np.ascontiguousarray(pins, np.int32)
+        part = np.ascontiguousarray(part, np.int32)
+        if len(pins) and int(pins.max()) >= len(part):
+            raise ValueError("part is shorter than the pins' node range")
+        out = np.zeros(3, np.int64)
+        _chk(_lib.ek_kway_metrics(self._c, len(net_ptr) - 1, _p(net_ptr), _p(pins), _p(part), int(k), _p(out)),
+             "kway_metrics")
+        return tuple(int(x) for x in out)
+
+    def partition_kway(self, hgr, k, min_spectral=32, limit=-1, lanczos=None):
+        """k-way partition by recursive spectral bisection (ek_partition_kway).  lanczos: ek_lanczos_opts
+        fields to override for every bisection.  Returns (part id per node, result dict)."""
+        o = _kway_opts(k, min_spectral, limit, False, None, lanczos)
+        part = np.full(hgr.nodes, -1, np.int32)
+        r = KwayResult()
+        _chk(_lib.ek_partition_kway(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)), "partition_kway")
+        return part, _kway_result(r)
+
+    def partition_kway_file(self, path, k, min_spectral=32, limit=-1, write_results=True, out_dir=None,
+                            lanczos=None):
+        """The same from a .hgr file; write_results: results/<base>.part.<k> under out_dir
+        (ek_partition_kway_file).  Returns (part id per node, result dict)."""
+        o = _kway_opts(k, min_spectral, limit, write_results, out_dir, lanczos)
+        nodes = Hypergraph.read(path).nodes
+        part = np.full(nodes, -1, np.int32)
+        r = KwayResult()
+        _chk(_lib.ek_partition_kway_file(self._c, os.fsencode(path), ctypes.byref(o), _p(part), ctypes.byref(r)),
+             f"partition_kway_file {path}")
+        return part, _kway_result(r)
 
     def kl_run(self, limit=-1, cap=None):
         cap = min(self._n01) if cap is None else cap

@@ -22,6 +22,10 @@
 //                        basis32 0); default: partial reorthogonalisation, the
 //                        ncv/5 restart floor and the fp32 basis shadow
 //   --reorth full|partial  only the reorthogonalisation rule
+//   --k N                gKL2 <in.hgr> -EIG only: N-way partition by recursive
+//                        spectral bisection (ek_partition_kway_file) instead of
+//                        the bipartition -> results/<base>.part.<N>, one part
+//                        id per line in node order
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -40,12 +44,21 @@
 
 #include "ek_internal.hpp"
 
+// kway.cpp: ek_partition_kway_file with the results file on, for `--k`.  A weak
+// reference, so that the host sources still link without the k-way unit (the
+// sanitizer harness builds a fixed list of them); --k then fails cleanly.
+namespace ek {
+int kway_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, ek_kway_result* r)
+    __attribute__((weak));
+}
+
 namespace {
 
 struct Opts {
     std::string tool, input;
     bool eig = false, quiet = false, have_seed = false, deflate = true, teardown = true;
     int device = 0, ncv = 0;
+    int kway = 0;  // --k N (0: the bipartition)
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -228,6 +241,20 @@ int run_kl(const Opts& o) {
     return 0;
 }
 
+// gKL2 <in.hgr> -EIG --k N: one summary line, results/<base>.part.<N>
+int run_kway(const Opts& o) {
+    const auto t0 = clk::now();
+    CtxInit ci(o.device, o.teardown);
+    const ek_solve_opts so = solve_opts(o);
+    if (!ek::kway_file_for_cli) throw Fail{"this build carries no k-way path"};
+    ek_kway_result r{};
+    check(ek::kway_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, &r), "k-way partition");
+    std::printf("k-way: k %d, part sizes %lld..%lld, cut nets %lld, connectivity %lld, SOED %lld, %.3f s -> "
+                "results/%s.part.%d\n", r.k, (long long)r.part_min, (long long)r.part_max, (long long)r.cut_nets,
+                (long long)r.connectivity, (long long)r.soed, secs(t0), base_name(o.input).c_str(), r.k);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ek_cli_main(const char* tool_c, int argc, char** argv) {
@@ -256,6 +283,10 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             else if (a == "--ncv") o.ncv = std::stoi(need("--ncv"));
             else if (a == "--tol") o.tol = std::stod(need("--tol"));
             else if (a == "--quiet") o.quiet = true;
+            else if (a == "--k") {
+                o.kway = std::stoi(need("--k"));
+                if (o.kway < 2) throw Fail{"--k takes a part count of at least 2"};
+            }
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -286,6 +317,13 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         }
         o.input = pos[0];
         o.eig = pos.size() == 2 && pos[1] == "-EIG";
+        if (o.kway) {
+            if (o.tool != "gKL2" || !o.eig) {
+                std::printf("Usage: gKL2 <input_file> -EIG --k <parts>  (--k needs gKL2 and -EIG)\n");
+                return 1;
+            }
+            return run_kway(o);
+        }
         return run_kl(o);
     } catch (const Fail& e) {
         std::fprintf(stderr, e.msg.rfind("Error", 0) == 0 ? "%s\n" : "Error: %s\n", e.msg.c_str());

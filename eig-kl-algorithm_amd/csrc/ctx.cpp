@@ -222,6 +222,7 @@ struct ek_ctx {
     // the device for ek_kl_set_partition_fiedler, and that split's scratch
     DBuf fied, sp_out, sp_tmp;
     int64_t fied_n = 0;
+    DBuf rk_tmp;  // the rank split's per-block counts (ek_kl_set_partition_fiedler_rank)
 };
 
 Uploader::Uploader(ek_ctx* ctx, hipStream_t st, size_t total)
@@ -3252,6 +3253,122 @@ int ek_kl_set_partition_fiedler(ek_ctx* c, double* median_out, int64_t* n0_out, 
     if (median_out) *median_out = med;
     if (n0_out) *n0_out = n0;
     if (n1_out) *n1_out = n - n0;
+    return EK_OK;
+    EK_CATCH
+}
+
+}  // extern "C"
+
+namespace {
+// The rank split of v (device, n doubles) into the given lists: the key at
+// rank n1 - 1 by the median split's radix select, then kernels_kway.hip's
+// count and place.  Returns the side-0 count (one synchronisation).
+int64_t rank_split_on_device(ek_ctx* c, const double* v, int64_t n, int64_t n1, int32_t* order0, int32_t* order1,
+                             uint32_t* plist, uint8_t* side) {
+    hipStream_t s = c->stream;
+    const int ni = int(n);
+    c->sp_tmp.ensure(ek::dev::split_tmp_bytes(ni));
+    c->sp_out.ensure(64);
+    c->rk_tmp.ensure(ek::dev::rank_tmp_bytes(ni));
+    auto* keys = c->sp_out.as<unsigned long long>();
+    if (n1 > 0) ek::dev::split_select(s, c->sp_tmp.p, v, ni, unsigned(n1 - 1), unsigned(n1 - 1), keys);
+    else HIPCHK(hipMemsetAsync(keys, 0, 16, s));  // key 0: nothing lies below it, none of its equals is needed
+    unsigned* n0_dev = reinterpret_cast<unsigned*>(keys + 2);
+    ek::dev::rank_partition(s, c->rk_tmp.p, v, ni, keys, unsigned(n1), order0, order1, plist, side, n0_dev);
+    HIPCHK(hipGetLastError());
+    unsigned n0u = 0;
+    HIPCHK(hipMemcpyAsync(&n0u, n0_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (int64_t(n0u) != n - n1)
+        ek::fail(EK_EHIP, "rank split: side 0 got %u nodes, expected %lld", n0u, (long long)(n - n1));
+    return int64_t(n0u);
+}
+}  // namespace
+
+extern "C" {
+
+int ek_rank_split_device(ek_ctx* c, int64_t n, const double* v_host, int64_t n1, uint8_t* bits_out) {
+    EK_TRY
+    check_ctx(c);
+    if (n <= 0 || n > INT32_MAX - 1 || !v_host || !bits_out || n1 < 0 || n1 > n)
+        ek::fail(EK_EINVAL, "ek_rank_split_device: bad argument");
+    hipStream_t s = c->stream;
+    DBuf v, o0, o1, pl, sd;
+    upload(v, v_host, size_t(n), s);
+    o0.ensure(size_t(n) * 4);
+    o1.ensure(size_t(n) * 4);
+    pl.ensure(size_t(n) * 4);
+    sd.ensure(size_t(n));
+    rank_split_on_device(c, v.as<double>(), n, n1, o0.as<int32_t>(), o1.as<int32_t>(), pl.as<uint32_t>(),
+                         sd.as<uint8_t>());
+    HIPCHK(hipMemcpyAsync(bits_out, sd.p, size_t(n), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_kl_set_partition_fiedler_rank(ek_ctx* c, int64_t n1, int64_t* n0_out, int64_t* n1_out) {
+    EK_TRY
+    check_ctx(c);
+    if (!c->kl_graph_ready) ek::fail(EK_ESTATE, "ek_kl_set_partition_fiedler_rank before ek_kl_graph_setup");
+    const int64_t n = c->kl_n;
+    if (c->fied_n != n || n < 2)
+        ek::fail(EK_ESTATE, "ek_kl_set_partition_fiedler_rank: no Fiedler vector of %lld entries on this context",
+                 (long long)n);
+    if (n > INT32_MAX - 1) ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler_rank: %lld nodes", (long long)n);
+    if (n1 < 1 || n1 >= n)
+        ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler_rank: n1 = %lld outside [1, %lld)", (long long)n1, (long long)n);
+    c->kl_order0.ensure(size_t(n) * 4);
+    c->kl_order1.ensure(size_t(n) * 4);
+    c->kl_side_init.ensure(size_t(n));
+    c->kl_plist.ensure(size_t(n) * 4);
+    const int64_t n0 = rank_split_on_device(c, c->fied.as<double>(), n, n1, c->kl_order0.as<int32_t>(),
+                                            c->kl_order1.as<int32_t>(), c->kl_plist.as<uint32_t>(),
+                                            c->kl_side_init.as<uint8_t>());
+    partition_on_device(c, n0, n - n0);
+    if (n0_out) *n0_out = n0;
+    if (n1_out) *n1_out = n - n0;
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_kway_metrics(ek_ctx* c, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* part_host,
+                    int32_t k, int64_t out[3]) {
+    EK_TRY
+    check_ctx(c);
+    if (nets < 0 || !net_ptr || !out || k < 1 || k > 256 || net_ptr[0] != 0 || (net_ptr[nets] > 0 && (!pins || !part_host)))
+        ek::fail(EK_EINVAL, "ek_kway_metrics: bad argument");
+    const int64_t npins = net_ptr[nets];
+    for (int64_t e = 0; e < nets; ++e)
+        if (net_ptr[e + 1] < net_ptr[e]) ek::fail(EK_EINVAL, "ek_kway_metrics: net_ptr not monotone");
+    int32_t top = -1;
+    for (int64_t p = 0; p < npins; ++p) {
+        if (pins[p] < 0) ek::fail(EK_EINVAL, "ek_kway_metrics: pin %d", pins[p]);
+        top = std::max(top, pins[p]);
+    }
+    out[0] = out[1] = out[2] = 0;
+    if (nets == 0 || npins == 0) return EK_OK;
+    const int64_t nodes = int64_t(top) + 1;
+    std::vector<uint8_t> part8(static_cast<size_t>(nodes));
+    for (int64_t i = 0; i < nodes; ++i) {
+        if (part_host[i] < 0 || part_host[i] >= k)
+            ek::fail(EK_EINVAL, "ek_kway_metrics: part %d of node %lld outside [0, %d)", part_host[i], (long long)i, k);
+        part8[size_t(i)] = uint8_t(part_host[i]);
+    }
+    hipStream_t s = c->stream;
+    const int nb = ek::dev::kway_metrics_blocks(nets);
+    DBuf d_ptr, d_pins, d_part, d_out;
+    upload(d_ptr, net_ptr, size_t(nets) + 1, s);
+    upload(d_pins, pins, size_t(npins), s);
+    upload(d_part, part8.data(), size_t(nodes), s);
+    d_out.ensure(size_t(3) * size_t(nb) * sizeof(unsigned));
+    ek::dev::kway_metrics(s, nets, d_ptr.as<int64_t>(), d_pins.as<int32_t>(), d_part.as<uint8_t>(), d_out.as<unsigned>());
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned> parts(size_t(3) * size_t(nb));
+    HIPCHK(hipMemcpyAsync(parts.data(), d_out.p, parts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int j = 0; j < 3; ++j)
+        for (int b = 0; b < nb; ++b) out[j] += int64_t(parts[size_t(j) * size_t(nb) + size_t(b)]);
     return EK_OK;
     EK_CATCH
 }

@@ -155,6 +155,17 @@ void fiedler_vector(ek_ctx* ctx, int rank, int nranks, const ek_hgr& h, const ek
                     std::vector<double>& v, ek_lanczos_stats& st, double* t_laplacian, double* t_lanczos,
                     const std::function<void()>& after_laplacian = {}, double* t_spmv_setup = nullptr,
                     bool host_v = true);
+// The KL adjacency of h built on host threads and set up on the context with
+// the nets (solve.cpp), for a std::async beside a Lanczos solve: solve() and
+// the k-way recursion (kway.cpp) share it.  Errors come back as {status,
+// message}: the message was written to that thread's ek_last_error().
+struct ThreadStatus {
+    int code = EK_OK;
+    std::string msg;
+    std::unique_ptr<ek_csr> host_copy;  // (large graphs) for the caller to free off the path
+};
+ThreadStatus kl_graph_host(const std::function<ek_ctx*()>* get_ctx, const ek_hgr* h, int threads);
+int kl_graph_threads(bool beside_solve);
 }  // namespace ek
 
 // ---------------------------------------------------------------------------
@@ -674,6 +685,21 @@ void kl_replay(hipStream_t s, int n, const uint8_t* side_init, const ek_swap* lo
 int net_cut_blocks(int64_t nets);
 void net_cut(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* side_a,
              const uint8_t* side_b, const uint8_t* side_c, unsigned* part);
+
+// kernels_kway.hip — the k-way path's rank split and metrics
+// blocks' counts of the rank split (tmp of rank_partition)
+size_t rank_tmp_bytes(int n);
+// the remain[] lists, plist and initial sides of the rank split: side 1 takes
+// every key below *key (device: the key at rank n1 - 1, from split_select)
+// and the smallest ids among the keys equal to it, n1 nodes in all; n0_out
+// (device): the side-0 count
+void rank_partition(hipStream_t s, void* tmp, const double* v, int n, const unsigned long long* key, unsigned n1,
+                    int32_t* order0, int32_t* order1, uint32_t* plist, uint8_t* side, unsigned* n0_out);
+// cut nets, connectivity and SOED of part[] (one byte per node) as
+// per-workgroup partials: metric j is the sum of out[j * kway_metrics_blocks(nets) + b]
+int kway_metrics_blocks(int64_t nets);
+void kway_metrics(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* part,
+                  unsigned* out);
 
 }  // namespace dev
 }  // namespace ek

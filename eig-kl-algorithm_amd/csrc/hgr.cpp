@@ -392,6 +392,61 @@ int ek_hgr_largest_component(const ek_hgr* h, ek_hgr** out, int32_t* node_map) {
     EK_CATCH
 }
 
+// Induced sub-hypergraph (the k-way recursion's blocks): every net restricted
+// to its kept pins, dropped when fewer than 2 remain.  Two passes over
+// contiguous net ranges on the host worker pool (host_threads() follows
+// EK_THREADS / OMP_NUM_THREADS, not the machine's core count): each range
+// counts its surviving nets and pins, then fills its slice of the output.
+int ek_hgr_induce(const ek_hgr* h, const uint8_t* keep, ek_hgr** out, int32_t* node_map) {
+    EK_TRY
+    if (!h || !keep || !out) ek::fail(EK_EINVAL, "ek_hgr_induce: null argument");
+    const int64_t n = h->nodes;
+    std::vector<int32_t> nid(static_cast<size_t>(n), -1);
+    int32_t m = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (keep[i]) nid[size_t(i)] = m++;
+    if (m == 0) ek::fail(EK_EINVAL, "ek_hgr_induce: no node kept");
+    const int64_t nets = h->nets, npins = int64_t(h->pins.size());
+    const int T = int(std::min<int64_t>(ek::host_threads(), std::max<int64_t>(1, npins / 65536)));
+    std::vector<int64_t> cn(size_t(T) + 1, 0), cp(size_t(T) + 1, 0);
+    auto kept_pins = [&](int64_t e) {
+        int64_t c = 0;
+        for (int64_t p = h->net_ptr[size_t(e)]; p < h->net_ptr[size_t(e) + 1]; ++p) c += nid[size_t(h->pins[size_t(p)])] >= 0;
+        return c;
+    };
+    ek::run_threads(T, [&](int t) {
+        int64_t a = 0, b = 0;
+        for (int64_t e = nets * t / T; e < nets * (t + 1) / T; ++e) {
+            const int64_t c = kept_pins(e);
+            if (c >= 2) ++a, b += c;
+        }
+        cn[size_t(t) + 1] = a;
+        cp[size_t(t) + 1] = b;
+    });
+    for (int t = 0; t < T; ++t) cn[size_t(t) + 1] += cn[size_t(t)], cp[size_t(t) + 1] += cp[size_t(t)];
+    auto c = std::make_unique<ek_hgr>();
+    c->nodes = m;
+    c->nets = cn[size_t(T)];
+    c->net_ptr.resize(size_t(c->nets) + 1);
+    c->pins.resize(size_t(cp[size_t(T)]));
+    c->net_ptr[0] = 0;
+    ek::run_threads(T, [&](int t) {
+        int64_t a = cn[size_t(t)], b = cp[size_t(t)];
+        for (int64_t e = nets * t / T; e < nets * (t + 1) / T; ++e) {
+            if (kept_pins(e) < 2) continue;
+            for (int64_t p = h->net_ptr[size_t(e)]; p < h->net_ptr[size_t(e) + 1]; ++p) {
+                const int32_t v = nid[size_t(h->pins[size_t(p)])];
+                if (v >= 0) c->pins[size_t(b++)] = v;
+            }
+            c->net_ptr[size_t(++a)] = b;
+        }
+    });
+    if (node_map) std::copy(nid.begin(), nid.end(), node_map);
+    *out = c.release();
+    return EK_OK;
+    EK_CATCH
+}
+
 int ek_hgr_write(const ek_hgr* h, const char* path) {
     EK_TRY
     if (!h || !path) ek::fail(EK_EINVAL, "ek_hgr_write: null argument");

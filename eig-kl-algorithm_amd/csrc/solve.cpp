@@ -42,13 +42,10 @@ void chk(int rc) {
 // one goes back to the caller, which frees it on another thread while the
 // KL loop runs: the 10x graph's ~100 MB took ~20 ms to unmap, and this
 // thread's end is on the path between Lanczos and KL there.
-// Its errors come back as {status, message}: the message was written to this
-// thread's ek_last_error(), which the caller's thread cannot see.
-struct ThreadStatus {
-    int code = EK_OK;
-    std::string msg;
-    std::unique_ptr<ek_csr> host_copy;  // (large graphs) for the caller to free off the path
-};
+// Its errors come back as {status, message} (ThreadStatus, ek_internal.hpp):
+// the message was written to this thread's ek_last_error(), which the
+// caller's thread cannot see.  Shared with the k-way recursion (kway.cpp).
+}  // namespace
 // The host build needs no context: in a fresh process it runs while the HIP
 // runtime starts (get_ctx waits for that only before the uploads).
 ThreadStatus kl_graph_host(const std::function<ek_ctx*()>* get_ctx, const ek_hgr* h, int threads) {
@@ -79,6 +76,7 @@ int kl_graph_threads(bool beside_solve) {
     if (const char* e = std::getenv("EK_KL_GRAPH_THREADS"); e && std::atoi(e) > 0) return std::atoi(e);
     return beside_solve ? std::max(1, host_threads() - 4) : 0;
 }
+namespace {
 
 // the results file's text buffer, kept across calls (one caller at a time)
 struct TextCache {

@@ -398,6 +398,104 @@ int ek_solve_file(ek_ctx* ctx, const char* path, const ek_solve_opts* o, ek_swap
                   ek_solve_result* res);
 
 /* ------------------------------------------------------------------ */
+/* k-way partitioning by recursive spectral bisection.  No reference     */
+/* counterpart anywhere in this section: the reference stops at two      */
+/* sides (cKL.cpp:151-197 splits once).                                  */
+/* ------------------------------------------------------------------ */
+/* The part sizes the recursion produces (host only).  A block of n' nodes
+ * that must become k' parts splits into side 0 with kL = ceil(k'/2) parts
+ * (ids [base, base+kL)) and side 1 with kR = floor(k'/2) parts (ids
+ * [base+kL, base+k')); side 1 gets n1 = floor(n' kR / k') nodes, side 0 the
+ * other n0 = n' - n1.  By induction every final part holds floor(n/k) or
+ * ceil(n/k) nodes: if floor(n'/k') <= n'/k' <= ceil(n'/k') then n1/kR =
+ * floor(n' kR/k')/kR lies in [floor(n'/k'), n'/k'] and n0/kL = ceil(n'
+ * kL/k')/kL in [n'/k', ceil(n'/k')], so both sides keep the same floor and
+ * ceiling as bounds of their own mean.  EK_EINVAL unless 2 <= k <= 256 and
+ * n >= 2k.  No reference counterpart. */
+int ek_kway_plan(int64_t n, int32_t k, int64_t* part_sizes /* k */);
+/* bits[i] = 1 for exactly the n1 nodes smallest in the key (ord(v[i]), i):
+ * ord is the order of the device's radix select (the fp64 bit patterns as a
+ * radix sort orders them: -0 before +0), ties broken by ascending node id.
+ * The orientation is ek_median_split's (median > v[i] gives bit 1).
+ * 0 <= n1 <= n.  No reference counterpart. */
+int ek_rank_split(int64_t n, const double* v, int64_t n1, uint8_t* bits_out);
+/* The sub-hypergraph on the nodes with keep[i] != 0, renumbered in ascending
+ * original id: every net restricted to its kept pins (so the clique weights
+ * of the sub-hypergraph use the restricted size: net splitting), nets left
+ * with fewer than 2 pins dropped, surviving nets in file order, pins in
+ * their original order.  node_map (nodes of h, may be NULL) gets the new id
+ * or -1, as ek_hgr_largest_component's.  EK_EINVAL when nothing is kept.
+ * No reference counterpart. */
+int ek_hgr_induce(const ek_hgr* h, const uint8_t* keep /* nodes */, ek_hgr** out, int32_t* node_map);
+/* Exact k-way quality of part[] (a part id in [0, k) per node, k <= 256),
+ * with lambda_e the number of distinct parts among net e's pins:
+ * out[0] = cut nets (lambda_e >= 2), out[1] = connectivity, the sum of
+ * (lambda_e - 1), out[2] = SOED, the sum of lambda_e over the cut nets.
+ * Host only.  No reference counterpart. */
+int ek_kway_metrics_host(int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* part, int32_t k,
+                         int64_t out[3]);
+/* ek_rank_split run by the device kernels on an uploaded copy of v_host (the
+ * radix select for the key at rank n1 - 1, a count of the keys below it, the
+ * equal keys taken in id order): the same bits.  The test seam of those
+ * kernels; needs no other setup on the context.  No reference counterpart. */
+int ek_rank_split_device(ek_ctx* ctx, int64_t n, const double* v_host, int64_t n1, uint8_t* bits_out);
+/* ek_kl_set_partition_fiedler with the rank split instead of the median
+ * split: side 1 (remain[1]) gets the n1 nodes ek_rank_split marks in the
+ * Fiedler vector the last ek_lanczos_fiedler left on the device, the lists in
+ * node order, no host round trip.  1 <= n1 < n.  n0_out / n1_out may be NULL.
+ * No reference counterpart. */
+int ek_kl_set_partition_fiedler_rank(ek_ctx* ctx, int64_t n1, int64_t* n0_out, int64_t* n1_out);
+/* ek_kway_metrics_host on the GPU (part_host is read up to the largest pin).
+ * No reference counterpart. */
+int ek_kway_metrics(ek_ctx* ctx, int64_t nets, const int64_t* net_ptr, const int32_t* pins,
+                    const int32_t* part_host, int32_t k, int64_t out[3]);
+
+typedef struct {
+    int32_t k;            /* number of parts, 2..256 */
+    int32_t min_spectral; /* blocks with fewer nodes are split by node index, not spectrally; default 32 */
+    int32_t limit;        /* KL termination limit of every bisection, as ek_solve_opts::limit */
+    int32_t write_results;/* ek_partition_kway_file: 1 writes results/<base>.part.<k> under out_dir */
+    const char* out_dir;  /* NULL: the CWD */
+    ek_lanczos_opts lanczos; /* for every bisection */
+} ek_kway_opts;
+
+#define EK_KWAY_LEVELS 8 /* depth of the recursion at k = 256 */
+typedef struct {
+    int32_t k;
+    int32_t bisections;      /* k - 1 */
+    int32_t fallback_splits; /* bisections split by node index (small block, no nets, or EK_ENOCONV) */
+    int32_t pad;
+    int64_t part_min, part_max;           /* smallest / largest part, in nodes */
+    int64_t cut_nets, connectivity, soed; /* ek_kway_metrics of part_out */
+    int64_t matvecs, kl_swaps;            /* totals over the bisections */
+    /* wall seconds (host clock): the sub-hypergraphs, Laplacian build +
+     * Lanczos, KL (adjacency wait, split, loop, sides), the metrics, all */
+    double t_induce, t_lanczos, t_kl, t_metrics, t_total;
+    double t_level[EK_KWAY_LEVELS]; /* per recursion level (root = 0), its blocks' induce + bisections */
+} ek_kway_result;
+
+void ek_kway_default_opts(ek_kway_opts* o);
+/* k-way partition of h by recursive bisection on this context, depth first,
+ * side 0 before side 1, one bisection at a time: the induced sub-hypergraph
+ * (ek_hgr_induce), its Laplacian built on the device (ek_spmv_setup_pins),
+ * the Fiedler vector (ek_lanczos_fiedler), the rank split at the block's
+ * ek_kway_plan size, then the KL loop on the block (ek_kl_run, best prefix).
+ * KL swaps pairs, so the planned sizes are exact in part_out (one id in
+ * [0, k) per node of h).  A block below min_spectral nodes, one with no net
+ * of >= 2 pins, or one whose Lanczos returns EK_ENOCONV is split by node
+ * index instead (its first n0 nodes to side 0; KL still runs when the block
+ * has nets); any other error ends the call.  EK_ESTATE on a multi-rank
+ * context (ek_comm_init* with nranks > 1).  result may be NULL.
+ * No reference counterpart. */
+int ek_partition_kway(ek_ctx* ctx, const ek_hgr* h, const ek_kway_opts* opts, int32_t* part_out /* nodes */,
+                      ek_kway_result* result);
+/* The same from a .hgr file; part_out may be NULL.  With write_results:
+ * results/<base>.part.<k> under out_dir, one part id per line in node order
+ * (the hMETIS partition-file convention).  No reference counterpart. */
+int ek_partition_kway_file(ek_ctx* ctx, const char* path, const ek_kway_opts* opts, int32_t* part_out,
+                           ek_kway_result* result);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
