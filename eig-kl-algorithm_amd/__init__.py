@@ -104,6 +104,20 @@ class KwayResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _KWAY_TIMES] + [("t_level", ctypes.c_double * KWAY_LEVELS)])
 
 
+class KwayRefineOpts(_AbiStruct):
+    _fields_ = [("k", _I32), ("max_rounds", _I32), ("imbalance", ctypes.c_double)]
+
+
+_REFINE_TIMES = ("t_setup", "t_rounds", "t_metrics")
+
+
+class KwayRefineResult(_AbiStruct):
+    _fields_ = ([("k", _I32), ("rounds", _I32)]
+                + [(k, _I64) for k in ("moves", "gain_total", "max_part", "part_min", "part_max",
+                                       "connectivity_before", "cut_nets", "connectivity", "soed")]
+                + [(k, ctypes.c_double) for k in _REFINE_TIMES])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -202,6 +216,11 @@ _sig("ek_kway_default_opts", None, ctypes.POINTER(KwayOpts))
 _sig("ek_partition_kway", ctypes.c_int, _P, _P, ctypes.POINTER(KwayOpts), _P, ctypes.POINTER(KwayResult))
 _sig("ek_partition_kway_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayOpts), _P,
      ctypes.POINTER(KwayResult))
+_sig("ek_kway_refine_default_opts", None, ctypes.POINTER(KwayRefineOpts))
+_sig("ek_kway_refine_host", ctypes.c_int, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _I64,
+     ctypes.POINTER(KwayRefineResult))
+_sig("ek_kway_refine", ctypes.c_int, _P, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _I64,
+     ctypes.POINTER(KwayRefineResult))
 
 lib = _lib
 
@@ -413,6 +432,34 @@ def _kway_result(r):
     out = {k: getattr(r, k) for k, _ in KwayResult._fields_ if k not in ("pad", "t_level")}
     out["t_level"] = list(r.t_level)
     return out
+
+
+def _kway_refine(call, what, hgr, part, k, imbalance, max_rounds):
+    """(refined part, result dict, round log): the log has one row per round that
+    moved, (candidates, independent candidates, accepted moves, gain)."""
+    start = np.ascontiguousarray(part, np.int32)
+    if len(start) != hgr.nodes:
+        raise ValueError(f"part has {len(start)} entries for {hgr.nodes} nodes")
+    o = KwayRefineOpts()
+    _lib.ek_kway_refine_default_opts(ctypes.byref(o))
+    o.k, o.max_rounds, o.imbalance = int(k), int(max_rounds), float(imbalance)
+    cap = int(max_rounds) if max_rounds > 0 else 1024
+    while True:
+        out = start.copy()
+        log = np.zeros((cap, 4), np.int64)
+        r = KwayRefineResult()
+        _chk(call(ctypes.byref(o), _p(out), _p(log), cap, ctypes.byref(r)), what)
+        if r.rounds <= cap:  # (else: deterministic, so the same run again with room for its log)
+            break
+        cap = r.rounds
+    return out, {name: getattr(r, name) for name, _ in KwayRefineResult._fields_}, log[:r.rounds].copy()
+
+
+def kway_refine_host(hgr, part, k, imbalance=0.03, max_rounds=0):
+    """k-way connectivity refinement under L_max = floor((1 + imbalance) ceil(n / k)), on the host
+    (ek_kway_refine_host, the device path's checker).  Returns (part, result dict, round log)."""
+    return _kway_refine(lambda *a: _lib.ek_kway_refine_host(hgr._h, *a), "kway_refine_host", hgr, part, k,
+                        imbalance, max_rounds)
 
 
 def eig_write(path, lam, median, bits, v):
@@ -678,6 +725,12 @@ class Context:
         r = KwayResult()
         _chk(_lib.ek_partition_kway(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)), "partition_kway")
         return part, _kway_result(r)
+
+    def kway_refine(self, hgr, part, k, imbalance=0.03, max_rounds=0):
+        """kway_refine_host on the GPU (ek_kway_refine): the same part vector, result integers and
+        round log.  Returns (part, result dict, round log)."""
+        return _kway_refine(lambda *a: _lib.ek_kway_refine(self._c, hgr._h, *a), "kway_refine", hgr, part, k,
+                            imbalance, max_rounds)
 
     def partition_kway_file(self, path, k, min_spectral=32, limit=-1, write_results=True, out_dir=None,
                             lanczos=None):

@@ -26,6 +26,11 @@
 //                        spectral bisection (ek_partition_kway_file) instead of
 //                        the bipartition -> results/<base>.part.<N>, one part
 //                        id per line in node order
+//   --refine EPS         with --k: then the k-way connectivity refinement on
+//                        the device (ek_kway_refine) with imbalance EPS; the
+//                        refined vector is what results/<base>.part.<N> holds,
+//                        and one more line beginning "refine:" is printed
+//   --refine-rounds R    at most R rounds of it (default: until none moves)
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -50,6 +55,9 @@
 namespace ek {
 int kway_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, ek_kway_result* r)
     __attribute__((weak));
+// kway_refine.cpp: the same followed by ek_kway_refine, for `--k N --refine EPS`
+int kway_refine_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                             int max_rounds, ek_kway_result* kr, ek_kway_refine_result* rr) __attribute__((weak));
 }
 
 namespace {
@@ -59,6 +67,9 @@ struct Opts {
     bool eig = false, quiet = false, have_seed = false, deflate = true, teardown = true;
     int device = 0, ncv = 0;
     int kway = 0;  // --k N (0: the bipartition)
+    bool refine = false;  // --refine EPS
+    double refine_eps = 0.0;
+    int refine_rounds = 0;  // --refine-rounds R (0: no limit)
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -248,10 +259,22 @@ int run_kway(const Opts& o) {
     const ek_solve_opts so = solve_opts(o);
     if (!ek::kway_file_for_cli) throw Fail{"this build carries no k-way path"};
     ek_kway_result r{};
-    check(ek::kway_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, &r), "k-way partition");
+    ek_kway_refine_result rr{};
+    if (o.refine) {
+        if (!ek::kway_refine_file_for_cli) throw Fail{"this build carries no k-way refinement"};
+        check(ek::kway_refine_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.refine_eps, o.refine_rounds,
+                                           &r, &rr), "k-way partition");
+    } else
+        check(ek::kway_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, &r), "k-way partition");
     std::printf("k-way: k %d, part sizes %lld..%lld, cut nets %lld, connectivity %lld, SOED %lld, %.3f s -> "
                 "results/%s.part.%d\n", r.k, (long long)r.part_min, (long long)r.part_max, (long long)r.cut_nets,
                 (long long)r.connectivity, (long long)r.soed, secs(t0), base_name(o.input).c_str(), r.k);
+    if (o.refine)
+        std::printf("refine: imbalance %g (max part %lld), %d rounds, %lld moves, connectivity %lld -> %lld, cut nets "
+                    "%lld, SOED %lld, part sizes %lld..%lld, %.3f s\n", o.refine_eps, (long long)rr.max_part, rr.rounds,
+                    (long long)rr.moves, (long long)rr.connectivity_before, (long long)rr.connectivity,
+                    (long long)rr.cut_nets, (long long)rr.soed, (long long)rr.part_min, (long long)rr.part_max,
+                    rr.t_setup + rr.t_rounds + rr.t_metrics);
     return 0;
 }
 
@@ -287,6 +310,11 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.kway = std::stoi(need("--k"));
                 if (o.kway < 2) throw Fail{"--k takes a part count of at least 2"};
             }
+            else if (a == "--refine") {
+                o.refine_eps = std::stod(need("--refine"));
+                o.refine = true;
+                if (!std::isfinite(o.refine_eps) || o.refine_eps < 0) throw Fail{"--refine takes an imbalance >= 0"};
+            } else if (a == "--refine-rounds") o.refine_rounds = std::stoi(need("--refine-rounds"));
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -317,6 +345,10 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         }
         o.input = pos[0];
         o.eig = pos.size() == 2 && pos[1] == "-EIG";
+        if (o.refine && !o.kway) {
+            std::printf("Usage: gKL2 <input_file> -EIG --k <parts> --refine <imbalance>  (--refine needs --k)\n");
+            return 1;
+        }
         if (o.kway) {
             if (o.tool != "gKL2" || !o.eig) {
                 std::printf("Usage: gKL2 <input_file> -EIG --k <parts>  (--k needs gKL2 and -EIG)\n");

@@ -166,6 +166,23 @@ struct ThreadStatus {
 };
 ThreadStatus kl_graph_host(const std::function<ek_ctx*()>* get_ctx, const ek_hgr* h, int threads);
 int kl_graph_threads(bool beside_solve);
+
+// kway.cpp: results/<base>.part.<k> under out_dir (null: the CWD), one id per line
+void write_part_file(const char* hgr_path, const char* out_dir, int32_t k, int64_t nodes, const int32_t* part);
+
+// kway_refine.cpp — what the host and the device refinement share: the input.
+// L_max = floor((1 + imbalance) ceil(n / k))
+int64_t refine_max_part(int64_t n, int32_t k, double imbalance);
+// the opts with the defaults filled in; EK_EINVAL as eigkl.h lists it
+ek_kway_refine_opts refine_check(const char* who, const ek_hgr* h, const ek_kway_refine_opts* opts,
+                                 const int32_t* part);
+// the nets of >= 2 distinct pins, in file order, each pin once (first
+// occurrence), and the node -> net incidence over them, nets ascending
+struct RefineInput {
+    std::vector<int64_t> net_ptr, inc_ptr;
+    std::vector<int32_t> pins, inc;
+};
+void refine_prepare(const ek_hgr& h, RefineInput& in);
 }  // namespace ek
 
 // ---------------------------------------------------------------------------
@@ -700,6 +717,21 @@ void rank_partition(hipStream_t s, void* tmp, const double* v, int n, const unsi
 int kway_metrics_blocks(int64_t nets);
 void kway_metrics(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* part,
                   unsigned* out);
+
+// kernels_refine.hip — one round of the k-way refinement (ek_kway_refine)
+struct RefineDev {
+    int n, nets, k, lmax;
+    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
+    const int32_t *pins, *inc;
+    uint8_t* part;              // n
+    int* sizes;                 // 256
+    unsigned long long* masks;  // 8 a net: Lambda(e), U(e)
+    unsigned long long *key, *win, *list, *thr;  // n, nets, n, 256
+    uint8_t* tgt;               // n
+};
+// slot (device, zero before the round): the round's candidates, independent
+// candidates, accepted moves and gain.  nets > 0.
+void refine_round(hipStream_t s, const RefineDev& d, unsigned long long* slot);
 
 }  // namespace dev
 }  // namespace ek

@@ -185,6 +185,21 @@ int kway_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opt
     if (lanczos) ko.lanczos = *lanczos;
     return ek_partition_kway_file(ctx, path, &ko, nullptr, r);
 }
+
+void write_part_file(const char* hgr_path, const char* out_dir, int32_t k, int64_t nodes, const int32_t* part) {
+    namespace fs = std::filesystem;
+    const fs::path dir = (out_dir && out_dir[0] ? fs::path(out_dir) : fs::path()) / "results";
+    std::error_code ec;
+    fs::create_directories(dir, ec);
+    const std::string out = (dir / (fs::path(hgr_path).filename().string() + ".part." + std::to_string(k))).string();
+    std::string text;
+    text.reserve(size_t(nodes) * 4);
+    for (int64_t i = 0; i < nodes; ++i) text += std::to_string(part[i]) + "\n";
+    FILE* f = std::fopen(out.c_str(), "w");
+    if (!f) fail(EK_EIO, "Error: Cannot open output file %s (%s)", out.c_str(), std::strerror(errno));
+    const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+    if ((std::fclose(f) != 0) || !ok) fail(EK_EIO, "short write to %s", out.c_str());
+}
 }  // namespace ek
 
 extern "C" {
@@ -285,20 +300,7 @@ int ek_partition_kway_file(ek_ctx* ctx, const char* path, const ek_kway_opts* op
     }
     ek_kway_result r{};
     partition(ctx, *h, opts, part_out, &r);
-    if (opts && opts->write_results) {
-        namespace fs = std::filesystem;
-        const fs::path dir = (opts->out_dir && opts->out_dir[0] ? fs::path(opts->out_dir) : fs::path()) / "results";
-        std::error_code ec;
-        fs::create_directories(dir, ec);
-        const std::string out = (dir / (fs::path(path).filename().string() + ".part." + std::to_string(r.k))).string();
-        std::string text;
-        text.reserve(size_t(h->nodes) * 4);
-        for (int64_t i = 0; i < h->nodes; ++i) text += std::to_string(part_out[i]) + "\n";
-        FILE* f = std::fopen(out.c_str(), "w");
-        if (!f) ek::fail(EK_EIO, "Error: Cannot open output file %s (%s)", out.c_str(), std::strerror(errno));
-        const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
-        if ((std::fclose(f) != 0) || !ok) ek::fail(EK_EIO, "short write to %s", out.c_str());
-    }
+    if (opts && opts->write_results) ek::write_part_file(path, opts->out_dir, r.k, h->nodes, part_out);
     if (result) *result = r;
     return EK_OK;
     EK_CATCH

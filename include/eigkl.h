@@ -496,6 +496,59 @@ int ek_partition_kway_file(ek_ctx* ctx, const char* path, const ek_kway_opts* op
                            ek_kway_result* result);
 
 /* ------------------------------------------------------------------ */
+/* k-way connectivity refinement under a maximum part size.  No          */
+/* reference counterpart (the reference stops at two sides).             */
+/* ------------------------------------------------------------------ */
+/* A deterministic, synchronous, integer-only refinement of the connectivity
+ * sum(lambda_e - 1) of a part vector.  Only nets with at
+ * least 2 distinct pins take part; a node repeated inside a net counts once.
+ * L_max = floor((1 + imbalance) ceil(n / k)); a part receives nodes only
+ * while it is below L_max, and there is no lower bound on a part's size.  One
+ * round, all of it read from the state at the round's start: every node takes
+ * as target the part b (below L_max, not its own) of greatest gain g = r + c_b
+ * - deg (r: its nets in which it is its part's only pin; c_b: its nets with a
+ * pin in b), ties to the smaller b, and is a candidate when g > 0; the winner
+ * of a net is its candidate pin of greatest g, ties to the smaller id; a
+ * candidate that wins every net it is on is independent; per target part the
+ * independent candidates in (g descending, id ascending) order are accepted
+ * while the part has room.  Accepted nodes share no net, so the connectivity
+ * falls by exactly the sum of their g.  Rounds repeat until one accepts
+ * nothing (that round is not counted) or max_rounds rounds have moved. */
+typedef struct {
+    int32_t k;          /* number of parts, 2..256 */
+    int32_t max_rounds; /* <= 0: until a round accepts nothing */
+    double imbalance;   /* epsilon >= 0; default 0.03 */
+} ek_kway_refine_opts;
+
+typedef struct {
+    int32_t k;
+    int32_t rounds;             /* rounds that moved at least one node */
+    int64_t moves;              /* accepted moves over all rounds */
+    int64_t gain_total;         /* sum of the rounds' gains = connectivity_before - connectivity */
+    int64_t max_part;           /* L_max */
+    int64_t part_min, part_max; /* smallest / largest part after the run, in nodes */
+    int64_t connectivity_before;
+    int64_t cut_nets, connectivity, soed; /* ek_kway_metrics of the refined vector */
+    double t_setup, t_rounds, t_metrics;  /* wall seconds (host clock) */
+} ek_kway_refine_result;
+
+void ek_kway_refine_default_opts(ek_kway_refine_opts* o);
+/* The refinement on the host (no GPU): the checker of ek_kway_refine, written
+ * from the rule.  part_inout: one id in [0, k) per node of h, refined in
+ * place.  round_log (may be NULL) receives four values per round, for the
+ * first log_rounds rounds: candidates, independent candidates, accepted
+ * moves, the round's gain.  EK_EINVAL for k outside 2..256, a part id outside
+ * [0, k), imbalance < 0 or not finite.  A part already above L_max is not an
+ * error: it never receives. */
+int ek_kway_refine_host(const ek_hgr* h, const ek_kway_refine_opts* opts, int32_t* part_inout, int64_t* round_log,
+                        int64_t log_rounds, ek_kway_refine_result* result);
+/* The same on the GPU: the same part vector, round log and result integers.
+ * The host reads one 8-byte counter per round.  EK_ESTATE on a multi-rank
+ * context.  Keeps nothing on the context: any other call may follow. */
+int ek_kway_refine(ek_ctx* ctx, const ek_hgr* h, const ek_kway_refine_opts* opts, int32_t* part_inout,
+                   int64_t* round_log, int64_t log_rounds, ek_kway_refine_result* result);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
