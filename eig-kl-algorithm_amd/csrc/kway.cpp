@@ -72,7 +72,11 @@ struct Kway {
         const int64_t n1 = n * kr / k, n0 = n - n1;
         bool edges = false;  // a net of >= 2 pins (an induced block's nets all are)
         for (int64_t e = 0; e < h.nets && !edges; ++e) edges = h.net_ptr[size_t(e) + 1] - h.net_ptr[size_t(e)] >= 2;
-        bool spectral = edges && n >= o.min_spectral;
+        // ek_lanczos_fiedler needs ncv = min(n/2, n - 1) > nev (1 deflated, 2
+        // not): below 4 nodes (6 undeflated) it answers EK_EINVAL, "graph too
+        // small", which is no EK_ENOCONV, so such a block takes the index split
+        const int64_t lanczos_min = o.lanczos.deflate ? 4 : 6;
+        bool spectral = edges && n >= std::max<int64_t>(o.min_spectral, lanczos_min);
         std::vector<uint8_t> sides(static_cast<size_t>(n));
         std::future<ek::ThreadStatus> kg;
         if (edges) kg = std::async(std::launch::async, ek::kl_graph_host, &get_ctx, &h, ek::kl_graph_threads(spectral));

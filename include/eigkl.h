@@ -452,7 +452,9 @@ int ek_kway_metrics(ek_ctx* ctx, int64_t nets, const int64_t* net_ptr, const int
 
 typedef struct {
     int32_t k;            /* number of parts, 2..256 */
-    int32_t min_spectral; /* blocks with fewer nodes are split by node index, not spectrally; default 32 */
+    int32_t min_spectral; /* blocks with fewer nodes are split by node index, not spectrally; default 32;
+                           * values below 4 act as 4 (6 with lanczos.deflate = 0): the smallest block
+                           * ek_lanczos_fiedler accepts */
     int32_t limit;        /* KL termination limit of every bisection, as ek_solve_opts::limit */
     int32_t write_results;/* ek_partition_kway_file: 1 writes results/<base>.part.<k> under out_dir */
     const char* out_dir;  /* NULL: the CWD */
@@ -481,7 +483,8 @@ void ek_kway_default_opts(ek_kway_opts* o);
  * the Fiedler vector (ek_lanczos_fiedler), the rank split at the block's
  * ek_kway_plan size, then the KL loop on the block (ek_kl_run, best prefix).
  * KL swaps pairs, so the planned sizes are exact in part_out (one id in
- * [0, k) per node of h).  A block below min_spectral nodes, one with no net
+ * [0, k) per node of h).  A block below min_spectral nodes (or below the 4
+ * nodes, 6 undeflated, that ek_lanczos_fiedler needs), one with no net
  * of >= 2 pins, or one whose Lanczos returns EK_ENOCONV is split by node
  * index instead (its first n0 nodes to side 0; KL still runs when the block
  * has nets); any other error ends the call.  EK_ESTATE on a multi-rank

@@ -132,6 +132,31 @@ def test_partition_kway_equals_reference_recursion(ek, ctx, hgrs, name, k, min_s
         assert res["kl_swaps"] == root_kl["iterations"]
 
 
+def test_partition_kway_min_spectral_below_lanczos_minimum(ek, ctx, hgrs):
+    """fract at k = 64 with min_spectral = 1: the last level bisects blocks of 4
+    and 5 nodes (every part keeps >= 2 nodes, so no smaller block is bisected).
+    ek_lanczos_fiedler takes them deflated (ncv = 2 > nev = 1) and refuses
+    them undeflated (ncv = 2 <= nev = 2) with EK_EINVAL, which is no
+    EK_ENOCONV and ended the whole call; such blocks now take the index split.
+    Either way: a valid partition with the planned sizes."""
+    h = hgrs["fract"]
+    k = 64
+    net_ptr, pins = h.pins()
+    for lanczos in (None, {"deflate": 0}):
+        part, res = ctx.partition_kway(h, k, min_spectral=1, lanczos=lanczos)
+        assert np.array_equal(np.bincount(part, minlength=k), ek.kway_plan(h.nodes, k))
+        assert part.min() == 0 and part.max() == k - 1
+        assert res["part_min"] == h.nodes // k and res["part_max"] == -(-h.nodes // k)
+        assert res["k"] == k and res["bisections"] == k - 1
+        assert (res["cut_nets"], res["connectivity"], res["soed"]) == ek.kway_metrics_host(net_ptr, pins, part, k)
+        if lanczos:
+            assert res["fallback_splits"] > 0  # the 4- and 5-node blocks
+            assert np.array_equal(part, ctx.partition_kway(h, k, min_spectral=6, lanczos=lanczos)[0])
+        else:
+            # min_spectral 1..3 act as 4, the smallest block the deflated solver takes
+            assert np.array_equal(part, ctx.partition_kway(h, k, min_spectral=4)[0])
+
+
 # ---------------------------------------------------------------------------
 # file form and CLI
 def _gkl2(*args, cwd):

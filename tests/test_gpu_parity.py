@@ -10,6 +10,7 @@ import pytest
 
 from conftest import (CIRCUITS, NET_CUTS, SWAP_MD5, PKG_DIR, circuit_path, compare_results_text, eig_path,
                       ref_results_path)
+from spmv_cases import sequential_rows as _sequential_rows  # the left-to-right row sum, shared with the shape tests
 
 pytestmark = pytest.mark.gpu
 
@@ -78,19 +79,6 @@ def test_spmv_dictionary_form_bit_identical(ek, ctx, monkeypatch, which):
     assert np.array_equal(out[False][0].view(np.uint64), out[True][0].view(np.uint64))
     assert out[False][1] == out[True][1] and out[False][3] == out[True][3]
     assert np.array_equal(out[False][2], out[True][2])
-
-
-def _sequential_rows(L, x):
-    """y[r] = (((0 + v0 x0) + v1 x1) + ...) over the row in ascending column
-    order: every product rounded, then added left to right (no FMA)."""
-    rp = L.rowptr.astype(np.int64)
-    ln = np.diff(rp)
-    y = np.zeros(len(ln))
-    for k in range(int(ln.max())):
-        live = ln > k
-        e = rp[:-1][live] + k
-        y[live] = y[live] + L.val[e] * x[L.col[e]]
-    return y
 
 
 @pytest.mark.parametrize("which", ["ibm01", "industry2", "syn0.25"])
