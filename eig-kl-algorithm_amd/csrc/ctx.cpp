@@ -1,229 +1,12 @@
-// GPU context, SpMV seam, implicitly restarted Lanczos driver and KL driver
+// GPU context, communicator, SpMV seam and implicitly restarted Lanczos driver
 // of libeigkl_hip.so (host code over the HIP runtime + RCCL).
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <atomic>
-#include <limits>
-#include <map>
-#include <memory>
-#include <tuple>
-
-#include "ek_internal.hpp"
+#include "ctx.hpp"
 
 #ifndef EK_UPD_RED_MAX_NRB
 #define EK_UPD_RED_MAX_NRB 256  // row blocks up to which the update workgroups sum the partials themselves
 #endif
 
-#define HIPCHK(call)                                                                                 \
-    do {                                                                                             \
-        const hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                      \
-            (void)hipGetLastError(); /* a failed call leaves no sticky error for the next entry */    \
-            ek::fail(EK_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-        }                                                                                            \
-    } while (0)
-#define NCCLCHK(call)                                                                                 \
-    do {                                                                                              \
-        const ncclResult_t r_ = (call);                                                               \
-        if (r_ != ncclSuccess) ek::fail(EK_ECOMM, "%s failed: %s", #call, ncclGetErrorString(r_));    \
-    } while (0)
-
-namespace {
-
-// Owning device allocation.
-struct DBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    DBuf() = default;
-    DBuf(const DBuf&) = delete;
-    DBuf& operator=(const DBuf&) = delete;
-    ~DBuf() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    void ensure(size_t b) {
-        if (b <= bytes && p) return;
-        reset();
-        HIPCHK(hipMalloc(&p, b ? b : 16));
-        bytes = b;
-    }
-    template <class T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
-
-template <class T>
-void upload(DBuf& d, const T* h, size_t n, hipStream_t s) {
-    d.ensure(n * sizeof(T));
-    if (n) HIPCHK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-}  // namespace
-
-// Setup uploads through the context's pinned staging: a copy from pageable
-// memory makes the runtime pin (or bounce) the user pages on every call,
-// which on freshly parsed arrays costs milliseconds; a memcpy into pinned
-// memory and an async DMA do not.  The caller sizes the arena for all the
-// uploads of one setup call and drains the stream before the next call.
-// The main stream and the KL stream each have an arena of their own: the KL
-// graph setup runs on ek_solve_file's host thread while the main thread
-// uploads the pins for the Laplacian build.
-struct Uploader {
-    ek_ctx* c;
-    hipStream_t s;
-    unsigned char*& buf;  // c->up (main stream) or c->kup (KL stream)
-    size_t& cap;
-    size_t off = 0;
-    Uploader(ek_ctx* ctx, hipStream_t st, size_t total);
-    template <class T>
-    void put(DBuf& d, const T* h, size_t n);
-};
-
-namespace {
-inline int64_t chunk_pad(int64_t n) { return std::max<int64_t>(round_up(n, ek::dev::KL_CHUNK_PAD), ek::dev::KL_CHUNK_PAD); }
-
-}  // namespace
-
-struct ek_ctx {
-    int device = 0;
-    int num_cu = 256;  // compute units (the panel SpMV's resident workgroups)
-    hipStream_t stream = nullptr;
-    // the KL graph's setup (ek_kl_graph_setup / ek_kl_nets_setup) runs on its
-    // own stream: ek_solve_file calls it from its host thread while the
-    // Lanczos solve occupies `stream`
-    hipStream_t kstream = nullptr;
-    // RCCL, or the host-staged exchange of ek_comm_init_host
-    ncclComm_t comm = nullptr;
-    int nranks = 1, rank = 0;
-    // the sharded layout and exchange (slot-padded all-gather, the one-all-
-    // reduce step): nranks > 1, or a forced 1-rank communicator (EK_COMM_FORCE,
-    // which runs the RCCL production path on one GPU: tests)
-    bool mr = false;
-    ek_allgather_fn host_ag = nullptr;
-    ek_allreduce_fn host_ar = nullptr;
-    void* host_user = nullptr;
-    double* stage = nullptr;  // pinned staging of the host-staged exchange
-    size_t stage_doubles = 0;
-    unsigned char* up = nullptr;  // pinned staging of the setup uploads on `stream` (see Uploader)
-    size_t up_bytes = 0;
-    unsigned char* kup = nullptr;  // ... and on `kstream`
-    size_t kup_bytes = 0;
-    double comm_ms = 0.0;     // host-observed time inside collectives (current solve)
-    int64_t n_ag = 0, n_ar = 0;  // collectives issued (current solve; sharded contexts)
-    // Laplacian rows owned by this context.  Sharded: rank r owns
-    // [shard_off[r], shard_off[r+1]) (nnz-balanced, so the slices differ);
-    // nloc = the largest slice; each rank's f is all-gathered into a slot of
-    // `slot` doubles (its rows, zero padding, its ||f||^2 partial at [ldv]),
-    // and the matrix's columns are remapped to that padded layout.
-    int64_t n = 0, row0 = 0, nrows = 0, nloc = 0, nnz = 0;
-    std::vector<int64_t> shard_off;
-    int64_t slot = 0;
-    DBuf off_d, xexp;
-    DBuf spx;  // ek_spmv's x in the all-gather layout (sharded), sized when the shard map is set
-    // The halo exchange of the sharded step (halo_build): instead of every
-    // rank's whole slot, each rank receives only the rows of f its columns
-    // read, into a compact x: block q (ranks in order) holds the rows of rank
-    // q this rank reads, ascending (its own block: all its rows), then q's
-    // ||f||^2 partial at the block end (hx_pidx[q]): one message per peer, the
-    // sender's packed rows closed by its partial.  The columns are remapped
-    // monotonically to it, so rows stay sorted and every product is summed in
-    // the same order as over the slot layout: the same bits.  Used where it
-    // moves fewer bytes than the all-gather (EK_MR_HALO=0/1 forces either).
-    bool halo = false;
-    int halo_calls = 0;  // halo_build calls since the shard map was set (exactly one per setup: it is collective)
-    std::vector<int64_t> hx_base;             // nranks + 1: block q at [hx_base[q], hx_base[q+1]), its partial last
-    std::vector<int64_t> hx_rcnt;             // rows received from q (own: nrows); the block is hx_rcnt[q] + 1
-    std::vector<int64_t> hx_scnt, hx_soff;    // rows sent to q, and that message's offset in hx_sbuf (+1: the partial)
-    std::vector<int64_t> hx_src;              // host-staged: q's message to this rank inside q's (padded) sbuf
-    std::vector<int32_t> hx_gidx_h;           // X[t]'s global row (-1: a partial slot)
-    int64_t hx_nsend = 0, hx_smax = 0;
-    DBuf hx_sidx, hx_sbuf, hx_X, hx_pidx, hx_gidx, hx_gbuf;
-    // exchange accounting (sharded solves): exchanges, point-to-point
-    // messages posted, and (with timing on) the exchanges' and all-reduces'
-    // durations on the device (HIP events around them on their streams) or,
-    // host-staged, as the host saw them
-    int64_t hx_exchanges = 0, hx_sends = 0, hx_recvs = 0;
-    double x_ms = 0.0, ar_ms = 0.0;
-    int64_t x_timed = 0, ar_timed = 0;
-    bool comm_time = false;
-    std::vector<hipEvent_t> cm_ev;            // event pool, reused across solves
-    std::vector<std::pair<int, int>> cm_rec;  // (kind: 0 exchange, 1 all-reduce; first event) of this solve
-    size_t cm_used = 0;
-    // the owned-slot part of a sharded rank's rows (plain CSR, local column
-    // ids), summed while the all-gather of the other slots runs on `gstream`
-    DBuf own_rowptr, own_col, own_val, own_rb, yown;
-    int own_nrb = 0;
-    int64_t own_nnz = 0;
-    bool own_ready = false;
-    hipStream_t gstream = nullptr;
-    hipEvent_t ag_ev[2] = {nullptr, nullptr};
-    // the column-panel form of the SpMV (pn_G > 0; kernels_panel.hip)
-    int pn_G = 0, pn_P = 0, pn_pb = 0, pn_max_rows = 0, pn_ndict = 0;
-    DBuf pn_wrow, pn_start, pn_word, pn_rid;
-    int block_nnz = 1024, nrb_spmv = 0;
-    bool spmv_long = true;  // a row block is one row longer than block_nnz (the SpMV's vector mode)
-    DBuf rb, rowptr, col, val, pk, rel, dict;
-    int colbits = 0;  // > 0: the dictionary-coded matrix (pk, dict) is the one the SpMV reads
-    int64_t mat_bytes = 0;  // bytes of the matrix arrays one SpMV reads, as stored
-    // Lanczos workspace
-    DBuf V, Vn, f, w, xfull, part, h1, h2, alpha, offd, fn2, npart, apart, Qd, scal, bov;
-    DBuf V32, Vn32;  // the basis's fp32 shadow (ek_lanczos_opts::basis32) and its restart buffer
-    DBuf fbk;        // launches whose fp32-shadow update fell back to V (a device counter)
-    DBuf actr;  // the SpMV's last-block counter (alpha hand-off), zero between launches
-    DBuf gctr;  // the projection's column-group counters (k_gemvt hand-off), zero between launches
-    // partial reorthogonalisation (reorth 3): the SpMV's ||w||^2 partials, the
-    // omega ring (3 x OMEGA_LD), k_pro's state and its per-step decisions
-    DBuf wpart, omega, prost, pflags;
-    DBuf cflag;  // the sharded step's cancellation flags (update_mr), one double per step
-    // HIP graphs of the single-context Lanczos step chunks (factorize_fused),
-    // keyed by (first step, end, run start, V, V32): captured on a chunk's
-    // second launch, replayed from its third; dropped when any buffer or
-    // parameter the launches carry changes (lz_sig)
-    std::map<std::tuple<int, int, int, const void*, const void*>, hipGraphExec_t> lz_graphs;
-    std::map<std::tuple<int, int, int, const void*, const void*>, int> lz_seen;
-    std::vector<uint64_t> lz_sig;
-    // KL state
-    int64_t kl_n = 0, kl_n0 = 0, kl_n1 = 0, kl_nets = 0;
-    DBuf kl_rowptr, kl_col, kl_w, kl_side, kl_side_init, kl_locked, kl_gp0, kl_gp1, kl_order0, kl_order1, kl_plist, kl_pinfo0, kl_pinfo1, kl_nd, kl_cinfo0, kl_cinfo1,
-        kl_ckey0, kl_ckey1, kl_aux, kl_seg, kl_cutpart, kl_cut0, kl_log, kl_out, kl_sides_tmp, kl_count, kl_netptr, kl_pins;
-    bool kl_graph_ready = false, kl_part_ready = false, kl_seg_ok = false, kl_segc_ok = false;
-    DBuf kl_segc, kl_wdict;
-    // device build of the Laplacian rows (ek_spmv_setup_pins)
-    DBuf lb_netptr, lb_pins, lb_icnt, lb_rcnt, lb_cur, lb_ip, lb_rp, lb_tiles, lb_inc, lb_scol, lb_sval, lb_tval,
-        lb_ulen, lb_len, lb_diag, lb_long, lb_cnt, lb_off, lb_table, lb_flags, lb_codes;
-    int kl_nwd = 0, kl_wcolbits = 0;
-    std::vector<int32_t> kl_rowptr_h;  // host copy (row descriptors)
-    std::vector<hipEvent_t> spmv_ev;   // SpMV timing events, created once per context
-    double* pin = nullptr;             // pinned host staging (Ritz vector + residual rows)
-    size_t pin_doubles = 0;
-    // mid-cycle convergence checks of the Lanczos driver: a copy stream, two
-    // pinned slots of {alpha, offd, fn2} and their events (created on first use)
-    hipStream_t cstream = nullptr;
-    hipEvent_t chk_done[2] = {nullptr, nullptr}, chk_copied[2] = {nullptr, nullptr};
-    hipEvent_t fin_ev = nullptr;  // the final Ritz vector's host copy landed
-    double* chk_pin = nullptr;
-    // the checks' completion words (EK_CHK_POLL): one per slot, 256 B apart, in
-    // pinned host memory the check's gather writes last; the host polls them
-    unsigned* chk_word = nullptr;
-    unsigned chk_seq = 0;
-    double* q_pin = nullptr;  // pinned staging of the restart's Q (MAX_NCV x (MAX_NCV + 1)), then the kept
-                              // projected matrix for k_pro (2 x (MAX_NCV + 2))
-    // the last Fiedler vector as returned (normalised, sign fixed), kept on
-    // the device for ek_kl_set_partition_fiedler, and that split's scratch
-    DBuf fied, sp_out, sp_tmp;
-    int64_t fied_n = 0;
-    DBuf rk_tmp;  // the rank split's per-block counts (ek_kl_set_partition_fiedler_rank)
-};
+using namespace ek::rt;
 
 Uploader::Uploader(ek_ctx* ctx, hipStream_t st, size_t total)
     : c(ctx), s(st), buf(st == ctx->kstream ? ctx->kup : ctx->up), cap(st == ctx->kstream ? ctx->kup_bytes : ctx->up_bytes) {
@@ -238,26 +21,7 @@ Uploader::Uploader(ek_ctx* ctx, hipStream_t st, size_t total)
     }
 }
 
-template <class T>
-void Uploader::put(DBuf& d, const T* h, size_t n) {
-    d.ensure(n * sizeof(T));
-    if (!n) return;
-    off = (off + 63) / 64 * 64;
-    if (off + n * sizeof(T) > cap) ek::fail(EK_EINVAL, "upload staging overflow");
-    std::memcpy(buf + off, h, n * sizeof(T));
-    HIPCHK(hipMemcpyAsync(d.p, buf + off, n * sizeof(T), hipMemcpyHostToDevice, s));
-    off += n * sizeof(T);
-}
-
 namespace {
-
-void set_device(ek_ctx* c) { HIPCHK(hipSetDevice(c->device)); }
-
-ek_ctx* check_ctx(ek_ctx* c) {
-    if (!c) ek::fail(EK_EINVAL, "null ek_ctx");
-    set_device(c);
-    return c;
-}
 
 ek::dev::SpmvMat spmv_mat(const ek_ctx* c) {
     ek::dev::SpmvMat m;
@@ -428,10 +192,7 @@ void comm_reset(ek_ctx* c) {
 }
 
 // EK_COMM_FORCE=1: a 1-rank communicator still takes the multi-rank path
-bool comm_forced() {
-    const char* e = std::getenv("EK_COMM_FORCE");
-    return e && e[0] && e[0] != '0';
-}
+bool comm_forced() { return env_flag("EK_COMM_FORCE", false); }
 
 }  // namespace
 
@@ -621,8 +382,7 @@ bool halo_build(ek_ctx* c, int32_t* col, int64_t nnz) {
     if (c->mr && ++c->halo_calls != 1)
         ek::fail(EK_ESTATE, "halo_build called %d times in one setup (a collective: once per rank)", c->halo_calls);
     if (!c->mr || c->nranks > ek::dev::MAX_HALO_RANKS) return false;
-    const char* env = std::getenv("EK_MR_HALO");
-    if (env && env[0] == '0') return false;
+    if (!env_flag("EK_MR_HALO", true)) return false;
     const int R = c->nranks, me = c->rank;
     const int64_t S = c->slot;
     const auto& off = c->shard_off;
@@ -667,7 +427,7 @@ bool halo_build(ek_ctx* c, int32_t* col, int64_t nnz) {
     }
     const int64_t full = int64_t(R) * int64_t(R - 1) * S;
     // (one forced rank: nothing to exchange either way; the slot layout)
-    const bool use = env && env[0] ? env[0] != '0' : R > 1 && double(tot_halo) <= 0.75 * double(full);
+    const bool use = env_flag("EK_MR_HALO", R > 1 && double(tot_halo) <= 0.75 * double(full));
     if (!use) return false;
     // the request lists, padded to the longest: rank r's request from this
     // rank starts at sum_{q < me, q != r} C[r][q] of r's list
@@ -803,8 +563,7 @@ void halo_exchange(ek_ctx* c, const double* src, hipStream_t st) {
 // forms took the same time inside the solve, 29 vs 30 us, and the 1x x
 // stays in every L2: tools/panel_lab.py)
 bool want_panels(const ek_ctx* c) {
-    if (const char* e = std::getenv("EK_SPMV_PANEL"); e && e[0]) return e[0] != '0';
-    return x_extent(c) * 8 > (int64_t(8) << 20);
+    return env_flag("EK_SPMV_PANEL", x_extent(c) * 8 > (int64_t(8) << 20));
 }
 
 // Build the panel layout from this rank's coded CSR on the device (rowptr_d,
@@ -814,7 +573,7 @@ bool build_panels(ek_ctx* c, hipStream_t s, const int32_t* rowptr_h, const int32
                   int colbits, int64_t ncodes) {
     const int64_t X = x_extent(c);
     int pb = 17;  // 1 MB of x per panel (EK_PANEL_PB: lab override)
-    if (const char* e = std::getenv("EK_PANEL_PB"); e && std::atoi(e) >= 10 && std::atoi(e) <= 24) pb = std::atoi(e);
+    if (const int e = env_int("EK_PANEL_PB", 0); e >= 10 && e <= 24) pb = e;
     while (((X + (int64_t(1) << pb) - 1) >> pb) > ek::dev::MAX_PANELS) ++pb;
     if (pb >= 32 || ncodes > (int64_t(1) << (32 - pb))) return false;
     const int P = int((X + (int64_t(1) << pb) - 1) >> pb);
@@ -959,9 +718,9 @@ void spmv_setup_rows(ek_ctx* c, int64_t n, const std::vector<int64_t>& off, cons
     std::vector<uint32_t> pkv;
     std::vector<double> dictv;
     int colbits = 0;
-    const char* plain = std::getenv("EK_SPMV_PLAIN");
+    const bool plain = env_flag("EK_SPMV_PLAIN", false);
     pt.mark("validate");
-    const bool packed = !(plain && plain[0] && plain[0] != '0') &&
+    const bool packed = !plain &&
                         ek::dev::spmv_pack(x_extent(c), nnz, col, val, pkv, dictv, colbits);
     pt.mark("pack");
     // 512-nnz blocks (tools/spmv_lab.hip for plain CSR; for the coded form,
@@ -1105,7 +864,7 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
     pt.mark("raw bound, shard map");
     hipStream_t s = c->stream;
     auto host_fallback = [&](const char* why) {
-        if (std::getenv("EK_TRACE")) std::fprintf(stderr, "[spmv_setup_pins] host build: %s\n", why);
+        if (env_set("EK_TRACE")) std::fprintf(stderr, "[spmv_setup_pins] host build: %s\n", why);
         ek_hgr h;
         h.nets = nets;
         h.nodes = n;
@@ -1116,7 +875,7 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
         spmv_setup_rows(c, n, off, L.rowptr.data(), L.col.data(), L.val64.data());
         if (on_device) *on_device = 0;
     };
-    if (std::getenv("EK_HOST_LAPLACIAN")) {
+    if (env_set("EK_HOST_LAPLACIAN")) {
         host_fallback("EK_HOST_LAPLACIAN");
         return EK_OK;
     }
@@ -1227,8 +986,7 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
     // the same greedy row blocks as the host path (ek_spmv_setup)
     int colbits = 1;
     while (colbits < 31 && (int64_t(1) << colbits) < x_extent(c)) ++colbits;
-    const char* plain_env = std::getenv("EK_SPMV_PLAIN");
-    bool packed = !(plain_env && plain_env[0] && plain_env[0] != '0') && colbits <= 28;
+    bool packed = !env_flag("EK_SPMV_PLAIN", false) && colbits <= 28;
     int64_t ncodes = 0;
     if (packed) {
         c->lb_table.ensure(size_t(TSIZE) * 8);
@@ -1376,8 +1134,7 @@ int ek_spmv_gather_bench(ek_ctx* c, int iters, double* avg_us) {
     // EK_GATHER_MODE (lab, kernels_spmv.hip k_lab_gather_step): 1 the gather +
     // a skipped step's update as two launches, 2 as one grid with an in-launch
     // wait, 3 the update alone; 0 (default) the gather-only ceiling
-    const char* gm = std::getenv("EK_GATHER_MODE");
-    const int mode = gm ? std::atoi(gm) : 0;
+    const int mode = env_int("EK_GATHER_MODE", 0);
     DBuf part, ctr, wv, fv, fpart;
     const int R = int(std::max<int64_t>(c->nrows, 1));
     if (mode) {
@@ -1679,7 +1436,7 @@ struct Lanczos {
     // cycle in chunks to check convergence between them)
     void factorize(int k, int kend) {
         // EK_LANCZOS_UNFUSED: run the sharded step sequence on one GPU (tests)
-        static const bool unfused = std::getenv("EK_LANCZOS_UNFUSED") != nullptr;
+        static const bool unfused = env_set("EK_LANCZOS_UNFUSED");
         if (reorth == 1) {
             if (!c->mr && !unfused) return graphs && !time_spmv ? factorize_graph(k, kend) : factorize_fused(k, kend);
             if (pro) return factorize_mr_pro(k, kend);
@@ -1907,10 +1664,7 @@ struct Lanczos {
     }
     void factorize_fused(int k, int kend) {
         // EK_LANCZOS_TT=0: the separate three-term launch (A/B; the same bits)
-        static const bool tt_fused = [] {
-            const char* e = std::getenv("EK_LANCZOS_TT");
-            return !(e && e[0] == '0');
-        }();
+        static const bool tt_fused = env_flag("EK_LANCZOS_TT", true);
         double* fn2 = c->fn2.as<double>();
         double* a3 = c->scal.as<double>() + 2;
         const double* bov = c->bov.as<double>();
@@ -1923,7 +1677,7 @@ struct Lanczos {
         unsigned* gctr = upd_red == 2 ? c->gctr.as<unsigned>() : nullptr;
         double* hoff = upd_red == 2 ? c->h2.as<double>() : nullptr;
         const bool inl = pro && proi && upd_red == 2;
-        static const bool pro_apart = std::getenv("EK_PRO_APART") != nullptr;  // (lab: k_pro + alpha re-reduced in the projection)
+        static const bool pro_apart = env_set("EK_PRO_APART");  // (lab: k_pro + alpha re-reduced in the projection)
         ek::dev::ProLaunch pl;
         if (inl) {
             pl.wpart = c->wpart.as<double>();
@@ -1942,10 +1696,7 @@ struct Lanczos {
             // tickets (dispatch-order independence): a launch whose grid is
             // not all resident at once takes them (pl.cap); EK_PRO_TICKETS=1
             // on every launch, =0 on none (logical index = blockIdx: A/B)
-            static const int tickets = [] {
-                const char* e = std::getenv("EK_PRO_TICKETS");
-                return e && e[0] ? (e[0] == '0' ? 0 : 2) : 1;
-            }();
+            static const int tickets = env_flag("EK_PRO_TICKETS", false) ? 2 : env_flag("EK_PRO_TICKETS", true) ? 1 : 0;
             if (tickets) pl.tix = pro_pub() + size_t(ek::dev::PRO_PUB_WORDS) * ek::dev::PRO_PUB_STRIDE;
             if (tickets == 1) {
                 pl.cap = ek::dev::gemvt_pro_capacity(nt, c->nrb_spmv > 12 * 256, pro_merge, pro_merge && b32,
@@ -1961,7 +1712,7 @@ struct Lanczos {
                 while (!pro_cgw_env && cg > 1 && grid(cg) > pl.cap) --cg;
                 if (!pro_cgw_env && cg > 0 && grid(cg) <= pl.cap) pl.cgw = cg;
             }
-            pl.rev = std::getenv("EK_DISPATCH_REVERSE") ? 1 : 0;
+            pl.rev = env_set("EK_DISPATCH_REVERSE") ? 1 : 0;
             if (pro_merge) {
                 pl.merged = 1;
                 pl.npart = c->npart.as<double>();
@@ -2224,8 +1975,7 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     // reorth 3: partial reorthogonalisation, on the single-context step and
     // on the sharded one (factorize_mr_pro; the CGS2 step always projects).
     // EK_REORTH=1|3 overrides (A/B).
-    int reorth_mode = o.reorth;
-    if (const char* e = std::getenv("EK_REORTH"); e && e[0]) reorth_mode = std::atoi(e);
+    const int reorth_mode = env_int("EK_REORTH", o.reorth);
     const int ncv_dflt = reorth_mode == 3 && n < 1000000 ? 80 : 100;
     int m = o.ncv > 0 ? o.ncv : int(std::min<int64_t>(ncv_dflt, n / 2));
     m = int(std::min<int64_t>(m, n - (deflate ? 1 : 0)));
@@ -2234,8 +1984,8 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     const double tol = o.tol > 0 ? o.tol : 1e-10;
     const int maxit = o.maxit > 0 ? o.maxit : 1000;
     const double eps23 = std::pow(std::numeric_limits<double>::epsilon(), 2.0 / 3.0);
-    const bool trace = std::getenv("EK_LANCZOS_TRACE") != nullptr;
-    const bool ortho_check = std::getenv("EK_LANCZOS_ORTHO") != nullptr;
+    const bool trace = env_set("EK_LANCZOS_TRACE");
+    const bool ortho_check = env_set("EK_LANCZOS_ORTHO");
     double ortho_max = 0.0;
 
     Lanczos L{};
@@ -2251,7 +2001,7 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     L.time_spmv = o.time_spmv != 0;
     L.reorth = o.reorth == 2 ? 2 : 1;
     hipStream_t s = c->stream;
-    L.pro = reorth_mode == 3 && L.reorth == 1 && std::getenv("EK_LANCZOS_UNFUSED") == nullptr;
+    L.pro = reorth_mode == 3 && L.reorth == 1 && !env_set("EK_LANCZOS_UNFUSED");
     // threshold 1e-10, not Simon's sqrt(eps): across implicit restarts the
     // kept Ritz block carries the basis's loss of orthogonality into the next
     // cycle, and the dropped projection coefficients (O(threshold) beta) stay
@@ -2268,8 +2018,8 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     // the launch's other waiters (kernels_lanczos.hip pro_poll), and the solve
     // fails with EK_EHIP.  EK_PRO_INLAUNCH=0 runs the step with no in-launch
     // wait at all.)
-    if (const char* e = std::getenv("EK_PRO_INLAUNCH"); L.pro && !c->mr) L.proi = !(e && e[0] == '0');
-    if (const char* e = std::getenv("EK_PRO_MERGE"); L.proi) L.pro_merge = !(e && e[0] == '0');
+    if (L.pro && !c->mr) L.proi = env_flag("EK_PRO_INLAUNCH", true);
+    if (L.proi) L.pro_merge = env_flag("EK_PRO_MERGE", true);
     // column groups walked per projection workgroup: about 850 projection
     // workgroups, at least 3 per row block (the 1.15x LCC, 207 row blocks:
     // 4; ibm01 / ibm10: one workgroup per tile as before).  A skipped step
@@ -2295,19 +2045,15 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     // the fp32 shadow: single-context three-term steps (the sharded and CGS2
     // steps project w itself, where h is not small)
     // (EK_BASIS32=0|1 / EK_ALPHA_LAST=0|1 override the options: A/B runs)
-    auto env_or = [](const char* k, bool dflt) {
-        const char* e = std::getenv(k);
-        return e && e[0] ? e[0] != '0' : dflt;
-    };
-    L.b32 = env_or("EK_BASIS32", o.basis32 != 0) && !c->mr && L.reorth == 1 &&
-            std::getenv("EK_LANCZOS_UNFUSED") == nullptr;
-    L.alpha_last = env_or("EK_ALPHA_LAST", o.alpha_last != 0);
+    L.b32 = env_flag("EK_BASIS32", o.basis32 != 0) && !c->mr && L.reorth == 1 &&
+            !env_set("EK_LANCZOS_UNFUSED");
+    L.alpha_last = env_flag("EK_ALPHA_LAST", o.alpha_last != 0);
     // non-temporal basis passes once the fp64 basis exceeds 768 MB (3x the
     // 256 MB MALL): it cannot stay there, and sweeping it through evicts the
     // matrix and x between SpMVs.  10x synthetic (1.6 GB): 404 -> 380 us per
     // matvec; at 300 MB (the 2x synthetics) the basis still profits from the
     // MALL (LCC 59.3 -> 61.2 ms with them).  EK_V_NT=0/1 forces either.
-    L.nt = env_or("EK_V_NT", ldv * size_t(m + 1) * 8 > (size_t(768) << 20));
+    L.nt = env_flag("EK_V_NT", ldv * size_t(m + 1) * 8 > (size_t(768) << 20));
     if (L.b32) {
         c->V32.ensure(ldv * size_t(m + 1) * 4);
         c->Vn32.ensure(ldv * size_t(m + 1) * 4);
@@ -2348,9 +2094,9 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     }
     // the step chunks' graphs (EK_LANCZOS_GRAPH=0: eager launches, A/B), kept
     // while every buffer and parameter their launches carry is unchanged
-    L.graphs = env_or("EK_LANCZOS_GRAPH", true) && !c->mr && L.reorth == 1;
+    L.graphs = env_flag("EK_LANCZOS_GRAPH", true) && !c->mr && L.reorth == 1;
     if (L.graphs) {
-        const int tt_env = std::getenv("EK_LANCZOS_TT") ? 1 : 0;
+        const int tt_env = env_set("EK_LANCZOS_TT") ? 1 : 0;
         auto pv = [](const void* p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
         auto db = [](double x) {
             uint64_t u;
@@ -2393,10 +2139,7 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
         // for the fence's L2 write-back (6-15 us at each of ~58 boundaries a
         // solve, kernel trace).  EK_CHK_FENCE: 0 system (the HIP default), 1
         // device-scope release (default), 2 no fence
-        static const int chk_fence = [] {
-            const char* e = std::getenv("EK_CHK_FENCE");
-            return e && e[0] ? std::atoi(e) : 1;
-        }();
+        static const int chk_fence = env_int("EK_CHK_FENCE", 1);
         const unsigned done_flags = hipEventDisableTiming | (chk_fence == 1   ? hipEventReleaseToDevice
                                                              : chk_fence == 2 ? hipEventDisableSystemFence
                                                                               : 0u);
@@ -2444,7 +2187,7 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     std::vector<ek::QRot> rots;
     std::vector<double> qscratch;
     // the restart's floor on the kept vectors (EK_KEEP_MIN overrides: A/B)
-    const int keep_min = std::getenv("EK_KEEP_MIN") ? std::atoi(std::getenv("EK_KEEP_MIN"))
+    const int keep_min = env_set("EK_KEEP_MIN")    ? std::atoi(std::getenv("EK_KEEP_MIN"))
                          : o.keep_min < 0                ? m / 5
                                                          : o.keep_min;
     int k = 0, restarts = 0, nconv = 0, injected = 0;
@@ -2461,21 +2204,15 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     };
     // the sharded step's re-projection of a cancelled f' (Lanczos::repair);
     // EK_LANCZOS_UNFUSED runs that step (and its flags) on a single context too
-    const bool mr_step = (c->mr || std::getenv("EK_LANCZOS_UNFUSED") != nullptr) && L.reorth == 1 && !L.pro;
+    const bool mr_step = (c->mr || env_set("EK_LANCZOS_UNFUSED")) && L.reorth == 1 && !L.pro;
     // the owned-slot / halo split of the sharded SpMV (EK_MR_OVERLAP=0: one
     // SpMV after the all-gather, the round-3 step; A/B and tests)
-    {
-        const char* e = std::getenv("EK_MR_OVERLAP");
-        L.overlap = c->mr && c->own_ready && !(e && e[0] == '0');
-    }
+    L.overlap = c->mr && c->own_ready && env_flag("EK_MR_OVERLAP", true);
     if (mr_step) {
         c->cflag.ensure(size_t(m + 2) * 8);  // (update_mr writes one flag per step)
         if (const char* e = std::getenv("EK_MR_CANCEL"); e && e[0]) L.mr_cancel = std::atof(e);  // (tests)
     }
-    const bool chk_kernel = [] {
-        const char* e = std::getenv("EK_CHK_KERNEL");
-        return !(e && e[0] == '0');
-    }();
+    const bool chk_kernel = env_flag("EK_CHK_KERNEL", true);
     // The mid-cycle check's gather on the compute stream itself, followed by
     // a completion word the host polls (EK_CHK_POLL=0: the event on the
     // compute stream, the gather on the copy stream, an event the host waits
@@ -2483,10 +2220,7 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
     // every chunk boundary (~12 us each, ~57 a solve); a kernel in the stream
     // is not.  The word is the gather's last store, made after every store of
     // the slot is released to the system (k_chk_gather).
-    const bool chk_poll = chk_kernel && [] {
-        const char* e = std::getenv("EK_CHK_POLL");
-        return !(e && e[0] == '0');
-    }();
+    const bool chk_poll = chk_kernel && env_flag("EK_CHK_POLL", true);
     // the host's wait for a slot's completion word (bounded: a kernel that
     // never ran must fail the solve, not hang the host)
     auto chk_wait = [&](int sl, unsigned seq) {
@@ -2811,7 +2545,7 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
         HIPCHK(hipStreamSynchronize(s));  // Q upload buffer reused next restart; fn2_k read (and k_pro's staging)
         fn2_k = *fn2_pin;
         restart_sync_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tsy).count();
-        if (L.pro && std::getenv("EK_PRO_TRACE")) {  // (lab: the cycle's per-step decisions)
+        if (L.pro && env_set("EK_PRO_TRACE")) {  // (lab: the cycle's per-step decisions)
             std::vector<int> fl(static_cast<size_t>(m));
             HIPCHK(hipMemcpy(fl.data(), c->pflags.p, size_t(m) * 4, hipMemcpyDeviceToHost));
             std::string row;
@@ -3016,685 +2750,6 @@ extern "C" int ek_lanczos_fiedler(ek_ctx* c, const ek_lanczos_opts* opts, double
             stats->update32_fallbacks = int32_t(fbn);
         }
     }
-    return EK_OK;
-    EK_CATCH
-}
-
-// ---------------------------------------------------------------------------
-// KL driver (KL(), cKL.cpp:288-406)
-extern "C" {
-
-int ek_kl_graph_setup(ek_ctx* c, int64_t n, const int32_t* rowptr, const int32_t* col, const float* w) {
-    EK_TRY
-    check_ctx(c);
-    ek::PhaseTimer pt("kl_graph_setup");
-    if (n <= 0 || n > INT32_MAX || !rowptr || !col || !w) ek::fail(EK_EINVAL, "ek_kl_graph_setup: bad argument");
-    const int64_t nnz = rowptr[n];
-    for (int64_t r = 0; r < n; ++r)
-        if (rowptr[r + 1] < rowptr[r]) ek::fail(EK_EINVAL, "ek_kl_graph_setup: rowptr not monotone");
-    {
-        std::atomic<bool> bad{false};
-        ek::parallel_for(nnz, [&](int64_t lo, int64_t hi) {
-            for (int64_t p = lo; p < hi; ++p)
-                if (col[p] < 0 || col[p] >= n) bad = true;
-        });
-        if (bad) ek::fail(EK_EINVAL, "ek_kl_graph_setup: column out of range");
-    }
-    pt.mark("checks");
-    hipStream_t s = c->kstream;
-    // not ready until this setup has finished: a failure part-way must not
-    // leave the previous graph's flags over this one's sizes
-    c->kl_graph_ready = false;
-    c->kl_part_ready = false;
-    c->kl_n = n;
-    c->kl_rowptr_h.assign(rowptr, rowptr + n + 1);
-    Uploader up(c, s, (size_t(n) + 1) * 4 + size_t(nnz) * 8 + size_t(nnz) * 4);
-    up.put(c->kl_rowptr, rowptr, size_t(n) + 1);
-    // 16 zero entries of tail padding: the swap loop reads rows 16 at a time unconditionally
-    c->kl_col.ensure((size_t(nnz) + 16) * 4);
-    c->kl_w.ensure((size_t(nnz) + 16) * 4);
-    HIPCHK(hipMemsetAsync(c->kl_col.as<int32_t>() + nnz, 0, 16 * 4, s));
-    HIPCHK(hipMemsetAsync(c->kl_w.as<float>() + nnz, 0, 16 * 4, s));
-    if (nnz) {
-        // (the staging copies on the host threads: ~9 MB at ibm18 shape)
-        unsigned char* const dc = up.buf + up.off;
-        unsigned char* const dw = dc + size_t(nnz) * 4;
-        ek::parallel_for(nnz, [&](int64_t lo, int64_t hi) {
-            std::memcpy(dc + size_t(lo) * 4, col + lo, size_t(hi - lo) * 4);
-            std::memcpy(dw + size_t(lo) * 4, w + lo, size_t(hi - lo) * 4);
-        });
-        HIPCHK(hipMemcpyAsync(c->kl_col.p, dc, size_t(nnz) * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->kl_w.p, dw, size_t(nnz) * 4, hipMemcpyHostToDevice, s));
-        up.off += size_t(nnz) * 8;
-    }
-    pt.mark("CSR staged");
-    // inline neighbour-row segments for the swap loop: weight-coded (128 B per
-    // entry) when the distinct weights fit the code bits and the LDS table,
-    // else plain (256 B per entry); skipped past 32 GB.  EK_KL_NOSEGC=1 at
-    // setup: plain (A/B, tests).
-    std::vector<uint32_t> kw;
-    std::vector<float> wdict;
-    int wcolbits = 0;
-    c->kl_segc_ok = !std::getenv("EK_KL_NOSEGC") &&
-                    size_t(nnz) * ek::dev::KL_SEGC_PIECES * sizeof(ek::dev::KLInfo) <= (size_t(32) << 30) &&
-                    ek::dev::kl_weight_codes(n, nnz, col, w, kw, wdict, wcolbits);
-    pt.mark("weight codes");
-    c->kl_seg_ok = !c->kl_segc_ok && size_t(nnz) * ek::dev::KL_SEG_LANES * sizeof(ek::dev::KLInfo) <= (size_t(32) << 30);
-    if (c->kl_segc_ok) {
-        DBuf dkw;
-        up.put(dkw, kw.data(), kw.size());
-        upload(c->kl_wdict, wdict.data(), wdict.size(), s);
-        c->kl_nwd = int(wdict.size());
-        c->kl_wcolbits = wcolbits;
-        c->kl_seg.reset();
-        c->kl_segc.ensure(size_t(std::max<int64_t>(nnz, 1)) * ek::dev::KL_SEGC_PIECES * sizeof(ek::dev::KLInfo));
-        ek::dev::kl_build_segc(s, nnz, c->kl_rowptr.as<int32_t>(), c->kl_col.as<int32_t>(), dkw.as<uint32_t>(),
-                               c->kl_segc.as<ek::dev::KLInfo>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));  // dkw is freed at scope end
-    }
-    if (c->kl_seg_ok) {
-        c->kl_segc.reset();
-        c->kl_seg.ensure(size_t(std::max<int64_t>(nnz, 1)) * ek::dev::KL_SEG_LANES * sizeof(ek::dev::KLInfo));
-        ek::dev::kl_build_seg(s, nnz, c->kl_rowptr.as<int32_t>(), c->kl_col.as<int32_t>(), c->kl_w.as<float>(),
-                              c->kl_seg.as<ek::dev::KLInfo>());
-        HIPCHK(hipGetLastError());
-    }
-    c->kl_side.ensure(size_t(n));
-    c->kl_side_init.ensure(size_t(n));
-    // (also the side / locked bitmaps of the on-chip loop when they exceed
-    // its LDS budget: 2 ceil(n/32) words, k_kl_swap_loop<.., GB>)
-    c->kl_locked.ensure(std::max(size_t(n), size_t((n + 31) / 32) * 8 + 64));
-    c->kl_plist.ensure(size_t(n) * 4);
-    c->kl_sides_tmp.ensure(size_t(n));
-    c->kl_cutpart.ensure(size_t((n + 255) / 256) * 8);
-    c->kl_cut0.ensure(16);
-    c->kl_out.ensure(sizeof(ek::dev::KLOut));
-    c->kl_count.ensure(64);
-    pt.mark("segments queued");
-    HIPCHK(hipStreamSynchronize(s));
-    pt.mark("synchronised");
-    c->kl_graph_ready = true;
-    c->kl_part_ready = false;
-    return EK_OK;
-    EK_CATCH
-}
-
-int ek_kl_nets_setup(ek_ctx* c, int64_t nets, const int64_t* net_ptr, const int32_t* pins) {
-    EK_TRY
-    check_ctx(c);
-    if (nets < 0 || !net_ptr || (net_ptr[nets] > 0 && !pins)) ek::fail(EK_EINVAL, "ek_kl_nets_setup: bad argument");
-    c->kl_nets = nets;
-    Uploader up(c, c->kstream, (size_t(nets) + 1) * 8 + size_t(net_ptr[nets]) * 4);
-    up.put(c->kl_netptr, net_ptr, size_t(nets) + 1);
-    up.put(c->kl_pins, pins, size_t(net_ptr[nets]));
-    c->kl_count.ensure(size_t(3) * size_t(ek::dev::net_cut_blocks(nets)) * sizeof(unsigned));  // ek_kl_run's cut partials
-    HIPCHK(hipStreamSynchronize(c->kstream));
-    return EK_OK;
-    EK_CATCH
-}
-
-}  // extern "C"
-
-namespace {
-// The rest of the partition setup once remain[] lists, plist and the initial
-// sides are on the device (uploaded, or split there from the Fiedler vector)
-void partition_on_device(ek_ctx* c, int64_t n0, int64_t n1) {
-    hipStream_t s = c->stream;
-    const int64_t n = c->kl_n;
-    c->kl_n0 = n0;
-    c->kl_n1 = n1;
-    // row descriptors: by position {node, rowptr, rowlen} and by node {rowptr,
-    // rowlen, plist}, built on the device from the lists just uploaded (the
-    // by-position arrays are padded to whole chunks with zero descriptors, and
-    // the gains with NaN = invalid keys, so the chunk scans load unconditionally)
-    {
-        c->kl_pinfo0.ensure(size_t(chunk_pad(n0)) * sizeof(ek::dev::KLInfo));
-        c->kl_pinfo1.ensure(size_t(chunk_pad(n1)) * sizeof(ek::dev::KLInfo));
-        c->kl_nd.ensure(size_t(std::max<int64_t>(n, 1)) * sizeof(ek::dev::KLInfo));
-        ek::dev::kl_build_desc(s, int(n), int(n0), int(n1), int(chunk_pad(n0)), int(chunk_pad(n1)),
-                               c->kl_order0.as<int32_t>(), c->kl_order1.as<int32_t>(), c->kl_plist.as<uint32_t>(),
-                               c->kl_rowptr.as<int32_t>(), c->kl_pinfo0.as<ek::dev::KLInfo>(),
-                               c->kl_pinfo1.as<ek::dev::KLInfo>(), c->kl_nd.as<ek::dev::KLInfo>());
-        HIPCHK(hipGetLastError());
-        const int64_t nnz = c->kl_rowptr_h[size_t(n)];
-        c->kl_aux.ensure(size_t(std::max<int64_t>(nnz, 1)) * sizeof(ek::dev::KLInfo));
-        ek::dev::kl_build_aux(s, nnz, c->kl_col.as<int32_t>(), c->kl_nd.as<ek::dev::KLInfo>(),
-                              c->kl_aux.as<ek::dev::KLInfo>());
-        HIPCHK(hipGetLastError());
-        c->kl_cinfo0.ensure(size_t((n0 + ek::dev::KL_CHUNK - 1) / ek::dev::KL_CHUNK + 1) * sizeof(ek::dev::KLInfo));
-        c->kl_cinfo1.ensure(size_t((n1 + ek::dev::KL_CHUNK - 1) / ek::dev::KL_CHUNK + 1) * sizeof(ek::dev::KLInfo));
-    }
-    c->kl_gp0.ensure(size_t(chunk_pad(n0)) * 4);
-    c->kl_gp1.ensure(size_t(chunk_pad(n1)) * 4);
-    HIPCHK(hipMemsetAsync(c->kl_gp0.p, 0xFF, c->kl_gp0.bytes, s));  // NaN padding
-    HIPCHK(hipMemsetAsync(c->kl_gp1.p, 0xFF, c->kl_gp1.bytes, s));
-    c->kl_ckey0.ensure(size_t((n0 + ek::dev::KL_CHUNK - 1) / ek::dev::KL_CHUNK + 1) * 8);
-    c->kl_ckey1.ensure(size_t((n1 + ek::dev::KL_CHUNK - 1) / ek::dev::KL_CHUNK + 1) * 8);
-    c->kl_log.ensure(size_t(std::max<int64_t>(1, std::min(n0, n1))) * sizeof(ek_swap));
-    HIPCHK(hipStreamSynchronize(s));
-    c->kl_part_ready = true;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ek_kl_set_partition(ek_ctx* c, const int32_t* order0, int64_t n0, const int32_t* order1, int64_t n1) {
-    EK_TRY
-    check_ctx(c);
-    if (!c->kl_graph_ready) ek::fail(EK_ESTATE, "ek_kl_set_partition before ek_kl_graph_setup");
-    const int64_t n = c->kl_n;
-    if (n0 < 0 || n1 < 0 || n0 + n1 != n || (n0 && !order0) || (n1 && !order1))
-        ek::fail(EK_EINVAL, "ek_kl_set_partition: the two lists must cover all %lld nodes", (long long)n);
-    std::vector<uint8_t> side(size_t(n), 2);
-    std::vector<uint32_t> plist(size_t(n), 0);
-    for (int64_t i = 0; i < n0; ++i) {
-        const int32_t u = order0[i];
-        if (u < 0 || u >= n || side[size_t(u)] != 2) ek::fail(EK_EINVAL, "ek_kl_set_partition: bad/duplicate node %d", u);
-        side[size_t(u)] = 0;
-        plist[size_t(u)] = uint32_t(i);
-    }
-    for (int64_t i = 0; i < n1; ++i) {
-        const int32_t u = order1[i];
-        if (u < 0 || u >= n || side[size_t(u)] != 2) ek::fail(EK_EINVAL, "ek_kl_set_partition: bad/duplicate node %d", u);
-        side[size_t(u)] = 1;
-        plist[size_t(u)] = uint32_t(i) | 0x80000000u;
-    }
-    hipStream_t s = c->stream;
-    Uploader up(c, s, size_t(n0) * 4 + size_t(n1) * 4 + size_t(n) + size_t(n) * 4);
-    up.put(c->kl_order0, order0, size_t(n0));
-    up.put(c->kl_order1, order1, size_t(n1));
-    up.put(c->kl_side_init, side.data(), size_t(n));
-    up.put(c->kl_plist, plist.data(), size_t(n));
-    partition_on_device(c, n0, n1);
-    return EK_OK;
-    EK_CATCH
-}
-
-int ek_kl_set_partition_fiedler(ek_ctx* c, double* median_out, int64_t* n0_out, int64_t* n1_out) {
-    EK_TRY
-    check_ctx(c);
-    if (!c->kl_graph_ready) ek::fail(EK_ESTATE, "ek_kl_set_partition_fiedler before ek_kl_graph_setup");
-    const int64_t n = c->kl_n;
-    if (c->fied_n != n || n < 1)
-        ek::fail(EK_ESTATE, "ek_kl_set_partition_fiedler: no Fiedler vector of %lld entries on this context",
-                 (long long)n);
-    if (n > INT32_MAX - 1) ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler: %lld nodes", (long long)n);
-    hipStream_t s = c->stream;
-    const int ni = int(n);
-    const double* v = c->fied.as<double>();
-    const size_t tb = ek::dev::split_tmp_bytes(ni);
-    c->sp_tmp.ensure(tb);
-    c->sp_out.ensure(64);
-    // the median: ranks n/2 (and n/2 - 1 for even n, their mean), the values
-    // nth_element gives ek_median_split (a radix select on the device)
-    const unsigned hi = unsigned(n / 2), lo = n % 2 == 0 ? hi - 1 : hi;
-    auto* keys = c->sp_out.as<unsigned long long>();
-    ek::dev::split_select(s, c->sp_tmp.p, v, ni, lo, hi, keys);
-    unsigned long long kk[2] = {0ull, 0ull};
-    HIPCHK(hipMemcpyAsync(kk, keys, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const double mid[2] = {ek::dev::key_value(kk[0]), ek::dev::key_value(kk[1])};
-    const double med = n % 2 == 0 ? (mid[0] + mid[1]) / 2.0 : mid[0];
-    c->kl_order0.ensure(size_t(n) * 4);
-    c->kl_order1.ensure(size_t(n) * 4);
-    c->kl_side_init.ensure(size_t(n));
-    c->kl_plist.ensure(size_t(n) * 4);
-    unsigned* n0_dev = reinterpret_cast<unsigned*>(c->sp_out.as<unsigned long long>() + 2);
-    ek::dev::split_partition(s, c->sp_tmp.p, v, ni, med, c->kl_order0.as<int32_t>(), c->kl_order1.as<int32_t>(),
-                             c->kl_plist.as<uint32_t>(), c->kl_side_init.as<uint8_t>(), n0_dev);
-    HIPCHK(hipGetLastError());
-    unsigned n0u = 0;
-    HIPCHK(hipMemcpyAsync(&n0u, n0_dev, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int64_t n0 = int64_t(n0u);
-    partition_on_device(c, n0, n - n0);
-    if (median_out) *median_out = med;
-    if (n0_out) *n0_out = n0;
-    if (n1_out) *n1_out = n - n0;
-    return EK_OK;
-    EK_CATCH
-}
-
-}  // extern "C"
-
-namespace {
-// The rank split of v (device, n doubles) into the given lists: the key at
-// rank n1 - 1 by the median split's radix select, then kernels_kway.hip's
-// count and place.  Returns the side-0 count (one synchronisation).
-int64_t rank_split_on_device(ek_ctx* c, const double* v, int64_t n, int64_t n1, int32_t* order0, int32_t* order1,
-                             uint32_t* plist, uint8_t* side) {
-    hipStream_t s = c->stream;
-    const int ni = int(n);
-    c->sp_tmp.ensure(ek::dev::split_tmp_bytes(ni));
-    c->sp_out.ensure(64);
-    c->rk_tmp.ensure(ek::dev::rank_tmp_bytes(ni));
-    auto* keys = c->sp_out.as<unsigned long long>();
-    if (n1 > 0) ek::dev::split_select(s, c->sp_tmp.p, v, ni, unsigned(n1 - 1), unsigned(n1 - 1), keys);
-    else HIPCHK(hipMemsetAsync(keys, 0, 16, s));  // key 0: nothing lies below it, none of its equals is needed
-    unsigned* n0_dev = reinterpret_cast<unsigned*>(keys + 2);
-    ek::dev::rank_partition(s, c->rk_tmp.p, v, ni, keys, unsigned(n1), order0, order1, plist, side, n0_dev);
-    HIPCHK(hipGetLastError());
-    unsigned n0u = 0;
-    HIPCHK(hipMemcpyAsync(&n0u, n0_dev, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (int64_t(n0u) != n - n1)
-        ek::fail(EK_EHIP, "rank split: side 0 got %u nodes, expected %lld", n0u, (long long)(n - n1));
-    return int64_t(n0u);
-}
-}  // namespace
-
-extern "C" {
-
-int ek_rank_split_device(ek_ctx* c, int64_t n, const double* v_host, int64_t n1, uint8_t* bits_out) {
-    EK_TRY
-    check_ctx(c);
-    if (n <= 0 || n > INT32_MAX - 1 || !v_host || !bits_out || n1 < 0 || n1 > n)
-        ek::fail(EK_EINVAL, "ek_rank_split_device: bad argument");
-    hipStream_t s = c->stream;
-    DBuf v, o0, o1, pl, sd;
-    upload(v, v_host, size_t(n), s);
-    o0.ensure(size_t(n) * 4);
-    o1.ensure(size_t(n) * 4);
-    pl.ensure(size_t(n) * 4);
-    sd.ensure(size_t(n));
-    rank_split_on_device(c, v.as<double>(), n, n1, o0.as<int32_t>(), o1.as<int32_t>(), pl.as<uint32_t>(),
-                         sd.as<uint8_t>());
-    HIPCHK(hipMemcpyAsync(bits_out, sd.p, size_t(n), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return EK_OK;
-    EK_CATCH
-}
-
-int ek_kl_set_partition_fiedler_rank(ek_ctx* c, int64_t n1, int64_t* n0_out, int64_t* n1_out) {
-    EK_TRY
-    check_ctx(c);
-    if (!c->kl_graph_ready) ek::fail(EK_ESTATE, "ek_kl_set_partition_fiedler_rank before ek_kl_graph_setup");
-    const int64_t n = c->kl_n;
-    if (c->fied_n != n || n < 2)
-        ek::fail(EK_ESTATE, "ek_kl_set_partition_fiedler_rank: no Fiedler vector of %lld entries on this context",
-                 (long long)n);
-    if (n > INT32_MAX - 1) ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler_rank: %lld nodes", (long long)n);
-    if (n1 < 1 || n1 >= n)
-        ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler_rank: n1 = %lld outside [1, %lld)", (long long)n1, (long long)n);
-    c->kl_order0.ensure(size_t(n) * 4);
-    c->kl_order1.ensure(size_t(n) * 4);
-    c->kl_side_init.ensure(size_t(n));
-    c->kl_plist.ensure(size_t(n) * 4);
-    const int64_t n0 = rank_split_on_device(c, c->fied.as<double>(), n, n1, c->kl_order0.as<int32_t>(),
-                                            c->kl_order1.as<int32_t>(), c->kl_plist.as<uint32_t>(),
-                                            c->kl_side_init.as<uint8_t>());
-    partition_on_device(c, n0, n - n0);
-    if (n0_out) *n0_out = n0;
-    if (n1_out) *n1_out = n - n0;
-    return EK_OK;
-    EK_CATCH
-}
-
-int ek_kway_metrics(ek_ctx* c, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* part_host,
-                    int32_t k, int64_t out[3]) {
-    EK_TRY
-    check_ctx(c);
-    if (nets < 0 || !net_ptr || !out || k < 1 || k > 256 || net_ptr[0] != 0 || (net_ptr[nets] > 0 && (!pins || !part_host)))
-        ek::fail(EK_EINVAL, "ek_kway_metrics: bad argument");
-    const int64_t npins = net_ptr[nets];
-    for (int64_t e = 0; e < nets; ++e)
-        if (net_ptr[e + 1] < net_ptr[e]) ek::fail(EK_EINVAL, "ek_kway_metrics: net_ptr not monotone");
-    int32_t top = -1;
-    for (int64_t p = 0; p < npins; ++p) {
-        if (pins[p] < 0) ek::fail(EK_EINVAL, "ek_kway_metrics: pin %d", pins[p]);
-        top = std::max(top, pins[p]);
-    }
-    out[0] = out[1] = out[2] = 0;
-    if (nets == 0 || npins == 0) return EK_OK;
-    const int64_t nodes = int64_t(top) + 1;
-    std::vector<uint8_t> part8(static_cast<size_t>(nodes));
-    for (int64_t i = 0; i < nodes; ++i) {
-        if (part_host[i] < 0 || part_host[i] >= k)
-            ek::fail(EK_EINVAL, "ek_kway_metrics: part %d of node %lld outside [0, %d)", part_host[i], (long long)i, k);
-        part8[size_t(i)] = uint8_t(part_host[i]);
-    }
-    hipStream_t s = c->stream;
-    const int nb = ek::dev::kway_metrics_blocks(nets);
-    DBuf d_ptr, d_pins, d_part, d_out;
-    upload(d_ptr, net_ptr, size_t(nets) + 1, s);
-    upload(d_pins, pins, size_t(npins), s);
-    upload(d_part, part8.data(), size_t(nodes), s);
-    d_out.ensure(size_t(3) * size_t(nb) * sizeof(unsigned));
-    ek::dev::kway_metrics(s, nets, d_ptr.as<int64_t>(), d_pins.as<int32_t>(), d_part.as<uint8_t>(), d_out.as<unsigned>());
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned> parts(size_t(3) * size_t(nb));
-    HIPCHK(hipMemcpyAsync(parts.data(), d_out.p, parts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int j = 0; j < 3; ++j)
-        for (int b = 0; b < nb; ++b) out[j] += int64_t(parts[size_t(j) * size_t(nb) + size_t(b)]);
-    return EK_OK;
-    EK_CATCH
-}
-
-// The k-way refinement on the device (kernels_refine.hip): six launches a
-// round, then ONE 8-byte read (the round's accepted moves) to learn whether to
-// go on.  The rounds' four counters stay in a device log of RF_LOG rounds,
-// read in bulk when it is full and at the end.  Every buffer is local to the
-// call: the context keeps nothing.
-int ek_kway_refine(ek_ctx* c, const ek_hgr* h, const ek_kway_refine_opts* opts, int32_t* part, int64_t* round_log,
-                   int64_t log_rounds, ek_kway_refine_result* result) {
-    EK_TRY
-    using clk = std::chrono::steady_clock;
-    auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
-    const auto t0 = clk::now();
-    check_ctx(c);
-    if (c->nranks > 1)
-        ek::fail(EK_ESTATE, "ek_kway_refine: a multi-rank context (%d ranks); k-way runs on one", c->nranks);
-    const ek_kway_refine_opts o = ek::refine_check("ek_kway_refine", h, opts, part);
-    const int64_t n = h->nodes;
-    ek::RefineInput in;
-    ek::refine_prepare(*h, in);
-    const int64_t nets = int64_t(in.net_ptr.size()) - 1;
-    ek_kway_refine_result r{};
-    r.k = o.k;
-    r.max_part = ek::refine_max_part(n, o.k, o.imbalance);
-    std::vector<int> sizes(256, 0);
-    for (int64_t i = 0; i < n; ++i) ++sizes[size_t(part[i])];
-    auto minmax = [&] {
-        r.part_min = *std::min_element(sizes.begin(), sizes.begin() + o.k);
-        r.part_max = *std::max_element(sizes.begin(), sizes.begin() + o.k);
-    };
-    minmax();
-    if (nets == 0) {  // nothing to refine, nothing cut
-        r.t_setup = since(t0);
-        if (result) *result = r;
-        return EK_OK;
-    }
-    hipStream_t s = c->stream;
-    std::vector<uint8_t> part8(static_cast<size_t>(n));
-    for (int64_t i = 0; i < n; ++i) part8[size_t(i)] = uint8_t(part[i]);
-    constexpr int64_t RF_LOG = 1024;
-    DBuf d_ptr, d_pins, d_iptr, d_inc, d_part, d_sizes, d_masks, d_key, d_win, d_list, d_thr, d_tgt, d_log, d_met;
-    upload(d_ptr, in.net_ptr.data(), in.net_ptr.size(), s);
-    upload(d_pins, in.pins.data(), in.pins.size(), s);
-    upload(d_iptr, in.inc_ptr.data(), in.inc_ptr.size(), s);
-    upload(d_inc, in.inc.data(), in.inc.size(), s);
-    upload(d_part, part8.data(), part8.size(), s);
-    upload(d_sizes, sizes.data(), sizes.size(), s);
-    d_masks.ensure(size_t(nets) * 64);
-    d_key.ensure(size_t(n) * 8);
-    d_win.ensure(size_t(nets) * 8);
-    d_list.ensure(size_t(n) * 8);
-    d_thr.ensure(256 * 8);
-    d_tgt.ensure(size_t(n));
-    d_log.ensure(size_t(RF_LOG) * 32);
-    HIPCHK(hipMemsetAsync(d_log.p, 0, size_t(RF_LOG) * 32, s));
-    const int nb = ek::dev::kway_metrics_blocks(nets);
-    d_met.ensure(size_t(3) * size_t(nb) * sizeof(unsigned));
-    std::vector<unsigned> partial(size_t(3) * size_t(nb));
-    auto metrics = [&](int64_t m[3]) {
-        ek::dev::kway_metrics(s, nets, d_ptr.as<int64_t>(), d_pins.as<int32_t>(), d_part.as<uint8_t>(),
-                              d_met.as<unsigned>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(partial.data(), d_met.p, partial.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (int j = 0; j < 3; ++j) {
-            m[j] = 0;
-            for (int b = 0; b < nb; ++b) m[j] += int64_t(partial[size_t(j) * size_t(nb) + size_t(b)]);
-        }
-    };
-    int64_t m[3];
-    metrics(m);
-    r.connectivity_before = m[1];
-    r.t_setup = since(t0);
-
-    const auto tr = clk::now();
-    ek::dev::RefineDev d{};
-    d.n = int(n);
-    d.nets = int(nets);
-    d.k = o.k;
-    d.lmax = int(std::min<int64_t>(r.max_part, INT32_MAX));
-    d.net_ptr = d_ptr.as<int64_t>();
-    d.inc_ptr = d_iptr.as<int64_t>();
-    d.pins = d_pins.as<int32_t>();
-    d.inc = d_inc.as<int32_t>();
-    d.part = d_part.as<uint8_t>();
-    d.sizes = d_sizes.as<int>();
-    d.masks = d_masks.as<unsigned long long>();
-    d.key = d_key.as<unsigned long long>();
-    d.win = d_win.as<unsigned long long>();
-    d.list = d_list.as<unsigned long long>();
-    d.thr = d_thr.as<unsigned long long>();
-    d.tgt = d_tgt.as<uint8_t>();
-    std::vector<unsigned long long> log;  // 4 a round, the rounds that moved
-    auto flush = [&](int64_t rows) {
-        const size_t at = log.size();
-        log.resize(at + size_t(rows) * 4);
-        if (rows) HIPCHK(hipMemcpyAsync(log.data() + at, d_log.p, size_t(rows) * 32, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    };
-    for (;;) {
-        if (o.max_rounds > 0 && r.rounds >= o.max_rounds) break;
-        const int64_t at = int64_t(r.rounds) % RF_LOG;
-        if (at == 0 && r.rounds > 0) {
-            flush(RF_LOG);
-            HIPCHK(hipMemsetAsync(d_log.p, 0, size_t(RF_LOG) * 32, s));
-        }
-        unsigned long long* slot = d_log.as<unsigned long long>() + 4 * at;
-        ek::dev::refine_round(s, d, slot);
-        HIPCHK(hipGetLastError());
-        unsigned long long accepted = 0;
-        HIPCHK(hipMemcpyAsync(&accepted, slot + 2, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (accepted == 0) break;
-        // every moving round lowers the connectivity by at least 1
-        if (r.rounds >= r.connectivity_before || r.rounds == INT32_MAX)
-            ek::fail(EK_EHIP, "ek_kway_refine: %d rounds moved from a connectivity of %lld", r.rounds + 1,
-                     (long long)r.connectivity_before);
-        ++r.rounds;
-    }
-    flush(int64_t(r.rounds) - int64_t(log.size() / 4));
-    r.t_rounds = since(tr);
-
-    const auto tm = clk::now();
-    for (int64_t i = 0; i < r.rounds; ++i) {
-        r.moves += int64_t(log[size_t(i) * 4 + 2]);
-        r.gain_total += int64_t(log[size_t(i) * 4 + 3]);
-    }
-    if (round_log)
-        for (int64_t i = 0; i < std::min<int64_t>(r.rounds, log_rounds) * 4; ++i) round_log[i] = int64_t(log[size_t(i)]);
-    HIPCHK(hipMemcpyAsync(part8.data(), d_part.p, part8.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(sizes.data(), d_sizes.p, sizes.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    metrics(m);  // (drains the stream: the two copies have landed)
-    for (int64_t i = 0; i < n; ++i) part[i] = part8[size_t(i)];
-    minmax();
-    r.cut_nets = m[0];
-    r.connectivity = m[1];
-    r.soed = m[2];
-    r.t_metrics = since(tm);
-    if (result) *result = r;
-    return EK_OK;
-    EK_CATCH
-}
-
-int ek_kl_set_partition_bits(ek_ctx* c, int64_t n, const uint8_t* bits) {
-    EK_TRY
-    if (n < 0 || (n && !bits)) ek::fail(EK_EINVAL, "ek_kl_set_partition_bits: bad argument");
-    std::vector<int32_t> o[2];
-    o[0].reserve(size_t(n) / 2 + 1);
-    o[1].reserve(size_t(n) / 2 + 1);
-    for (int64_t i = 0; i < n; ++i) {
-        if (bits[i] > 1) ek::fail(EK_EINVAL, "ek_kl_set_partition_bits: bit %d at node %lld", int(bits[i]), (long long)i);
-        o[bits[i]].push_back(int32_t(i));
-    }
-    return ek_kl_set_partition(c, o[0].data(), int64_t(o[0].size()), o[1].data(), int64_t(o[1].size()));
-    EK_CATCH
-}
-
-}  // extern "C"
-
-namespace {
-
-ek::dev::KLDev kl_dev(ek_ctx* c) {
-    ek::dev::KLDev d;
-    d.n = int(c->kl_n);
-    d.nnz = c->kl_rowptr_h.empty() ? 0 : c->kl_rowptr_h.back();
-    d.rowptr = c->kl_rowptr.as<int32_t>();
-    d.col = c->kl_col.as<int32_t>();
-    d.w = c->kl_w.as<float>();
-    d.side = c->kl_side.as<uint8_t>();
-    d.side_init = c->kl_side_init.as<uint8_t>();
-    d.locked = c->kl_locked.as<uint8_t>();
-    d.gp0 = c->kl_gp0.as<float>();
-    d.gp1 = c->kl_gp1.as<float>();
-    d.order0 = c->kl_order0.as<int32_t>();
-    d.order1 = c->kl_order1.as<int32_t>();
-    d.plist = c->kl_plist.as<uint32_t>();
-    d.pinfo0 = c->kl_pinfo0.as<ek::dev::KLInfo>();
-    d.pinfo1 = c->kl_pinfo1.as<ek::dev::KLInfo>();
-    d.nd = c->kl_nd.as<ek::dev::KLInfo>();
-    d.cinfo0 = c->kl_cinfo0.as<ek::dev::KLInfo>();
-    d.cinfo1 = c->kl_cinfo1.as<ek::dev::KLInfo>();
-    d.aux = c->kl_aux.as<ek::dev::KLInfo>();
-    const bool noseg = std::getenv("EK_KL_NOSEG") != nullptr;  // env: A/B, no inline segments at all
-    d.seg = c->kl_seg_ok && !noseg ? c->kl_seg.as<ek::dev::KLInfo>() : nullptr;
-    d.segc = c->kl_segc_ok && !noseg ? c->kl_segc.as<ek::dev::KLInfo>() : nullptr;
-    d.wdict = c->kl_wdict.as<float>();
-    d.nwd = c->kl_nwd;
-    d.wcolbits = c->kl_wcolbits;
-    d.n0 = int(c->kl_n0);
-    d.n1 = int(c->kl_n1);
-    d.nck0 = int((c->kl_n0 + ek::dev::KL_CHUNK - 1) / ek::dev::KL_CHUNK);
-    d.nck1 = int((c->kl_n1 + ek::dev::KL_CHUNK - 1) / ek::dev::KL_CHUNK);
-    d.ckey0 = c->kl_ckey0.as<unsigned long long>();
-    d.ckey1 = c->kl_ckey1.as<unsigned long long>();
-    d.cut_part = c->kl_cutpart.as<double>();
-    d.cut0 = c->kl_cut0.as<float>();
-    return d;
-}
-
-}  // namespace
-
-extern "C" int ek_kl_run(ek_ctx* c, int32_t limit, ek_swap* log_out, int64_t cap, ek_kl_result* res) {
-    EK_TRY
-    check_ctx(c);
-    if (!c->kl_graph_ready || !c->kl_part_ready) ek::fail(EK_ESTATE, "ek_kl_run before graph/partition setup");
-    hipStream_t s = c->stream;
-    const int64_t n = c->kl_n;
-    const int lim = limit >= 0 ? limit : int(std::log2(double(n))) + 5;  // cKL.cpp:303
-    const auto d = kl_dev(c);
-    hipEvent_t e0, e1, e2;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventCreate(&e2));
-    struct G {
-        hipEvent_t a, b, c;
-        ~G() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
-            (void)hipEventDestroy(c);
-        }
-    } guard{e0, e1, e2};
-    const long long dcap = std::max<int64_t>(1, std::min(c->kl_n0, c->kl_n1));
-    auto* out = c->kl_out.as<ek::dev::KLOut>();
-    HIPCHK(hipEventRecord(e0, s));
-    HIPCHK(hipMemcpyAsync(c->kl_side.p, c->kl_side_init.p, size_t(n), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemsetAsync(c->kl_locked.p, 0, size_t(n), s));
-    ek::dev::kl_prepare(s, d);
-    HIPCHK(hipEventRecord(e1, s));
-    ek::dev::kl_loop(s, d, lim, c->kl_log.as<ek_swap>(), dcap, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e2, s));
-    // integer net cuts: initial, best prefix, final
-    const bool nets = c->kl_nets > 0;
-    const int ncb = nets ? ek::dev::net_cut_blocks(c->kl_nets) : 0;
-    std::vector<unsigned> cparts(size_t(3) * size_t(ncb));
-    if (nets) {  // one pass over the pins for all three; per-workgroup counts, added here
-        ek::dev::kl_replay(s, int(n), c->kl_side_init.as<uint8_t>(), c->kl_log.as<ek_swap>(), &out->best_iter, dcap,
-                           c->kl_sides_tmp.as<uint8_t>());
-        ek::dev::net_cut(s, c->kl_nets, c->kl_netptr.as<int64_t>(), c->kl_pins.as<int32_t>(),
-                         c->kl_side_init.as<uint8_t>(), c->kl_sides_tmp.as<uint8_t>(), c->kl_side.as<uint8_t>(),
-                         c->kl_count.as<unsigned>());
-    }
-    ek::dev::KLOut ho{};
-    HIPCHK(hipMemcpyAsync(&ho, out, sizeof ho, hipMemcpyDeviceToHost, s));
-    if (nets)
-        HIPCHK(hipMemcpyAsync(cparts.data(), c->kl_count.p, cparts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (ho.status == 3u)
-        ek::fail(EK_EHIP, "KL swap loop: an in-launch wait gave up (EK_KL_PIPE=0 runs the loop without them)");
-    unsigned long long hc[3] = {0, 0, 0};
-    for (int k = 0; k < 3; ++k)
-        for (int b = 0; b < ncb; ++b) hc[k] += cparts[size_t(k) * size_t(ncb) + size_t(b)];
-    if (log_out && cap > 0) {
-        const int64_t k = std::min<int64_t>(cap, ho.iterations);
-        if (k) HIPCHK(hipMemcpy(log_out, c->kl_log.p, size_t(k) * sizeof(ek_swap), hipMemcpyDeviceToHost));
-    }
-    if (res) {
-        float loop_ms = 0.f, prep_ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&prep_ms, e0, e1));
-        HIPCHK(hipEventElapsedTime(&loop_ms, e1, e2));
-        res->iterations = ho.iterations;
-        res->initial_cut = ho.initial_cut;
-        res->best_cut = ho.best_cut;
-        res->final_cut = ho.final_cut;
-        res->best_iter = ho.best_iter;
-        res->net_cut_initial = nets ? int64_t(hc[0]) : -1;
-        res->net_cut_best = nets ? int64_t(hc[1]) : -1;
-        res->net_cut_final = nets ? int64_t(hc[2]) : -1;
-        res->loop_ms = loop_ms;
-        if (std::getenv("EK_KL_PROF") && ho.prof[13] == 0x9199ull) {  // the overlapped loop (k_kl_swap_pipe)
-            const double sw = double(std::max<long long>(1, ho.iterations)), gs = double(std::max<unsigned long long>(1, ho.prof[2]));
-            std::fprintf(stderr, "[kl-pipe] %lld swaps: speculated %.1f %%, hits %.1f %%; loop %.0f cycles/swap\n",
-                         (long long)ho.iterations, 100.0 * double(ho.prof[0]) / sw, 100.0 * double(ho.prof[1]) / gs,
-                         double(ho.prof[12]) / sw);
-            std::fprintf(stderr, "[kl-pipe] gain wave 0, cycles/swap: pair wait %.0f, P %.0f, speculative rows %.0f (per "
-                         "speculation), pair->barrier1 %.0f\n", double(ho.prof[3]) / gs, double(ho.prof[4]) / gs,
-                         double(ho.prof[5]) / double(std::max<unsigned long long>(1, ho.prof[0])), double(ho.prof[6]) / gs);
-            std::fprintf(stderr, "[kl-pipe] W wave, cycles/swap: barrier-2 wait %.0f, selection %.0f, pair->barrier1 %.0f, "
-                         "G2 span %.0f; G2a wave's G2 span %.0f\n", double(ho.prof[7]) / sw, double(ho.prof[8]) / sw,
-                         double(ho.prof[9]) / sw, double(ho.prof[10]) / sw, double(ho.prof[11]) / sw);
-        } else if (std::getenv("EK_KL_PROF")) {
-            static const char* names[12] = {"select", "G1-key", "bar1", "G2a", "G2bc", "bar2", "G1-aux", "G1-sum",
-                                            "n_stale", "n_late+tail", "G1-load", "G1-look"};
-            std::fprintf(stderr, "[kl] %lld swaps, us/swap:", (long long)ho.iterations);
-            for (int i = 0; i < 12; ++i)
-                std::fprintf(stderr, " %s %.3f", names[i], ho.prof[i] * 0.01 / std::max<long long>(1, ho.iterations));
-            std::fprintf(stderr, "\n");
-            if (ho.prof[15])
-                std::fprintf(stderr, "[kl] in-loop shader clock %.0f MHz\n", double(ho.prof[14]) / (double(ho.prof[15]) * 0.01));
-            if (ho.warr[0] || ho.warr[8]) {
-                const double cyc_ns = ho.prof[15] ? double(ho.prof[15]) * 10.0 / double(ho.prof[14]) : 1.0 / 2.4;
-                const double f = 1e-3 * cyc_ns / double(std::max<long long>(1, ho.iterations));
-                std::fprintf(stderr, "[kl] per wave, us after its loop top: selection done / barrier 1 / G2a done / barrier 2:\n");
-                std::fprintf(stderr, "[kl] prefetch predicted node1 in %.1f %%, node2 in %.1f %% of swaps\n",
-                             100.0 * double(ho.warr[40]) / double(std::max<long long>(1, ho.iterations)),
-                             100.0 * double(ho.warr[41]) / double(std::max<long long>(1, ho.iterations)));
-                for (int w = 0; w < 8; ++w)
-                    std::fprintf(stderr, "[kl]   w%d %.3f %.3f %.3f %.3f  (G2a reads consumed %.3f)\n", w,
-                                 f * double(ho.warr[24 + w]), f * double(ho.warr[w]), f * double(ho.warr[16 + w]),
-                                 f * double(ho.warr[8 + w]), f * double(ho.warr[32 + w]));
-            }
-        }
-        res->total_ms = double(loop_ms) + double(prep_ms);
-    }
-    return EK_OK;
-    EK_CATCH
-}
-
-extern "C" int ek_kl_sides(ek_ctx* c, int32_t which, uint8_t* sides_out) {
-    EK_TRY
-    check_ctx(c);
-    if (!c->kl_part_ready || !sides_out) ek::fail(EK_ESTATE, "ek_kl_sides: nothing to report");
-    hipStream_t s = c->stream;
-    const int64_t n = c->kl_n;
-    const uint8_t* src = c->kl_side_init.as<uint8_t>();
-    if (which == 2) src = c->kl_side.as<uint8_t>();
-    if (which == 1) {
-        const long long dcap = std::max<int64_t>(1, std::min(c->kl_n0, c->kl_n1));
-        ek::dev::kl_replay(s, int(n), c->kl_side_init.as<uint8_t>(), c->kl_log.as<ek_swap>(),
-                           &c->kl_out.as<ek::dev::KLOut>()->best_iter, dcap, c->kl_sides_tmp.as<uint8_t>());
-        src = c->kl_sides_tmp.as<uint8_t>();
-    }
-    HIPCHK(hipMemcpyAsync(sides_out, src, size_t(n), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
     return EK_OK;
     EK_CATCH
 }

@@ -1,4 +1,4 @@
-// k-way connectivity refinement (ek_kway_refine, ctx.cpp): the kernels of one
+// k-way connectivity refinement (ek_kway_refine, ctx_kway.cpp): the kernels of one
 // round.  A translation unit of its own: the code objects of the
 // bipartitioner's and the k-way path's kernels are what they were without it.
 //

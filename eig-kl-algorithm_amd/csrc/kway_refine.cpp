@@ -1,7 +1,7 @@
 // k-way connectivity refinement under a maximum part size: the host pieces.
 //
 // ek_kway_refine_host is the checker of the device path (ek_kway_refine,
-// ctx.cpp + kernels_refine.hip).  It is written from the rule (eigkl.h,
+// ctx_kway.cpp + kernels_refine.hip).  It is written from the rule (eigkl.h,
 // DESIGN.md §9), one plain loop per step of a round, not from the kernels:
 // per-part counters where the device keeps bit masks, a sort where the device
 // selects a threshold key.  The two share only what is input, not algorithm:

@@ -1,5 +1,5 @@
 // Test helper (tests/test_sanitizers.py only): the GPU-side C-ABI entry points
-// the host sources call (ctx.cpp is HIP code), as a machine without a usable
+// the host sources call (the ctx*.cpp files are HIP code), as a machine without a usable
 // gfx950 device sees them — every one fails with EK_EHIP like the real
 // library there — so the host code (CLI argument and file handling, the
 // solve pipeline up to the GPU, ingest, clique expansions, EIG I/O, the

@@ -6,6 +6,7 @@ when no device is present, and the drop-in CLIs' argument/file error paths
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -28,6 +29,26 @@ def test_every_declared_symbol_is_exported(ek):
     lib = ctypes.CDLL(LIB)
     missing = [s for s in names if not hasattr(lib, s)]
     assert not missing, missing
+
+
+def _defined_dynamic_symbols():
+    nm = shutil.which("nm") or shutil.which("llvm-nm", path=os.path.join(
+        os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"))
+    assert nm, "neither nm nor the ROCm tree's llvm-nm found"
+    out = subprocess.run([nm, "-D", "--defined-only", LIB], check=True, capture_output=True, text=True).stdout
+    return {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
+
+
+def test_header_and_dynamic_symbol_table_agree():
+    """The header is the C ABI's only record: every ek_ function it declares
+    is a defined dynamic symbol of the library (read from the symbol table;
+    nothing is loaded), and the library defines no ek_* C symbol the header
+    does not declare (C++ symbols are mangled, _ZN2ek..., and do not match)."""
+    declared = set(_declared())
+    defined = {s for s in _defined_dynamic_symbols() if re.fullmatch(r"ek_[a-z0-9_]+", s)}
+    assert len(declared) >= 35
+    assert sorted(declared - defined) == [], "declared in eigkl.h, not defined by the library"
+    assert sorted(defined - declared) == [], "defined by the library, not declared in eigkl.h"
 
 
 def test_struct_layout_matches_python_mirror(ek, tmp_path):
