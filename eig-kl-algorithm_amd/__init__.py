@@ -118,6 +118,18 @@ class KwayRefineResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _REFINE_TIMES])
 
 
+class SweepOpts(_AbiStruct):
+    _fields_ = [("objective", _I32), ("pad", _I32), ("imbalance", ctypes.c_double)]
+
+
+_SWEEP_TIMES = ("t_sort", "t_profile", "t_select")
+
+
+class SweepResult(_AbiStruct):
+    _fields_ = ([(k, _I64) for k in ("n", "n0", "n1", "s_lo", "s_hi", "max_part", "cut", "cut_mid", "spanning_nets")]
+                + [(k, ctypes.c_double) for k in _SWEEP_TIMES])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -221,6 +233,11 @@ _sig("ek_kway_refine_host", ctypes.c_int, _P, ctypes.POINTER(KwayRefineOpts), _P
      ctypes.POINTER(KwayRefineResult))
 _sig("ek_kway_refine", ctypes.c_int, _P, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _I64,
      ctypes.POINTER(KwayRefineResult))
+_sig("ek_sweep_default_opts", None, ctypes.POINTER(SweepOpts))
+_sig("ek_sweep_cut_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
+_sig("ek_sweep_cut", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
+_sig("ek_kl_set_partition_fiedler_sweep", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts),
+     ctypes.POINTER(SweepResult))
 
 lib = _lib
 
@@ -462,6 +479,36 @@ def kway_refine_host(hgr, part, k, imbalance=0.03, max_rounds=0):
                         imbalance, max_rounds)
 
 
+def _sweep_opts(imbalance, ratio):
+    o = SweepOpts()
+    _lib.ek_sweep_default_opts(ctypes.byref(o))
+    o.objective, o.imbalance = 1 if ratio else 0, float(imbalance)
+    return o
+
+
+def _sweep_result(r):
+    return {name: getattr(r, name) for name, _ in SweepResult._fields_}
+
+
+def _sweep_cut(call, what, hgr, v, imbalance, ratio):
+    v = np.ascontiguousarray(v, np.float64)
+    if len(v) != hgr.nodes:
+        raise ValueError(f"v has {len(v)} entries for {hgr.nodes} nodes")
+    o = _sweep_opts(imbalance, ratio)
+    order = np.full(len(v), -1, np.int32)
+    profile = np.full(len(v) + 1, -1, np.int32)
+    r = SweepResult()
+    _chk(call(_p(v), ctypes.byref(o), _p(order), _p(profile), ctypes.byref(r)), what)
+    return _sweep_result(r), order, profile
+
+
+def sweep_cut_host(hgr, v, imbalance=0.03, ratio=False):
+    """The sweep cut of v over hgr's nets inside the window of L_max = floor((1 + imbalance) ceil(n / 2)), on the
+    host (ek_sweep_cut_host, the device path's checker): the minimum cut, or with ratio the ratio cut.
+    Returns (result dict, order, profile): order[r] the node at rank r, profile[s] the nets cut by split s."""
+    return _sweep_cut(lambda *a: _lib.ek_sweep_cut_host(hgr._h, *a), "sweep_cut_host", hgr, v, imbalance, ratio)
+
+
 def eig_write(path, lam, median, bits, v):
     bits = np.ascontiguousarray(bits, np.uint8)
     v = np.ascontiguousarray(v, np.float64)
@@ -697,6 +744,21 @@ class Context:
              "kl_set_partition_fiedler_rank")
         self._n01 = (a.value, b.value)
         return a.value, b.value
+
+    def sweep_cut(self, hgr, v, imbalance=0.03, ratio=False):
+        """sweep_cut_host on the GPU, on an uploaded copy of v (ek_sweep_cut): the same order, profile and
+        result integers.  Returns (result dict, order, profile)."""
+        return _sweep_cut(lambda *a: _lib.ek_sweep_cut(self._c, hgr._h, *a), "sweep_cut", hgr, v, imbalance, ratio)
+
+    def kl_set_partition_fiedler_sweep(self, hgr, imbalance=0.03, ratio=False):
+        """The sweep cut of the Fiedler vector left on this context, then kl_set_partition_fiedler_rank at its
+        n1 (ek_kl_set_partition_fiedler_sweep).  Returns the result dict."""
+        o = _sweep_opts(imbalance, ratio)
+        r = SweepResult()
+        _chk(_lib.ek_kl_set_partition_fiedler_sweep(self._c, hgr._h, ctypes.byref(o), ctypes.byref(r)),
+             "kl_set_partition_fiedler_sweep")
+        self._n01 = (r.n0, r.n1)
+        return _sweep_result(r)
 
     def rank_split_device(self, v, n1):
         """rank_split run by the device kernels on an uploaded copy of v (ek_rank_split_device)."""

@@ -31,6 +31,14 @@
 //                        refined vector is what results/<base>.part.<N> holds,
 //                        and one more line beginning "refine:" is printed
 //   --refine-rounds R    at most R rounds of it (default: until none moves)
+//   --sweep EPS          gKL2 <in.hgr> -EIG only, not with --k: the sweep cut of
+//                        the Fiedler vector under imbalance EPS
+//                        (ek_kl_set_partition_fiedler_sweep) instead of the median
+//                        split, then the KL loop -> results/<base>.part.2, one
+//                        side per line in node order; one line beginning
+//                        "sweep:" is printed
+//   --sweep-ratio        with --sweep: the ratio cut c / (|A| |B|) instead of the
+//                        minimum cut
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -58,6 +66,10 @@ int kway_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opt
 // kway_refine.cpp: the same followed by ek_kway_refine, for `--k N --refine EPS`
 int kway_refine_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
                              int max_rounds, ek_kway_result* kr, ek_kway_refine_result* rr) __attribute__((weak));
+// sweep.cpp: the bipartition from the sweep cut, for `--sweep EPS`
+int sweep_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, int32_t limit, double imbalance,
+                       int ratio, ek_sweep_result* sr, ek_kl_result* kr, double* lambda, ek_lanczos_stats* st)
+    __attribute__((weak));
 }
 
 namespace {
@@ -70,6 +82,8 @@ struct Opts {
     bool refine = false;  // --refine EPS
     double refine_eps = 0.0;
     int refine_rounds = 0;  // --refine-rounds R (0: no limit)
+    bool sweep = false, sweep_ratio = false;  // --sweep EPS, --sweep-ratio
+    double sweep_eps = 0.0;
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -278,6 +292,26 @@ int run_kway(const Opts& o) {
     return 0;
 }
 
+// gKL2 <in.hgr> -EIG --sweep EPS [--sweep-ratio]: one summary line, results/<base>.part.2
+int run_sweep(const Opts& o) {
+    const auto t0 = clk::now();
+    CtxInit ci(o.device, o.teardown);
+    const ek_solve_opts so = solve_opts(o);
+    if (!ek::sweep_file_for_cli) throw Fail{"this build carries no sweep cut"};
+    ek_sweep_result r{};
+    ek_kl_result kr{};
+    double lambda = 0.0;
+    ek_lanczos_stats st{};
+    check(ek::sweep_file_for_cli(ci.get(), o.input.c_str(), &so.lanczos, so.limit, o.sweep_eps, o.sweep_ratio ? 1 : 0, &r,
+                                 &kr, &lambda, &st), "sweep cut");
+    std::printf("sweep: imbalance %g (%s), window %lld..%lld (max part %lld), n1 %lld, cut_mid %lld, cut %lld, "
+                "net_cut_best %lld (KL: %lld swaps, best prefix %lld), %.3f s -> results/%s.part.2\n", o.sweep_eps,
+                o.sweep_ratio ? "ratio cut" : "minimum cut", (long long)r.s_lo, (long long)r.s_hi, (long long)r.max_part,
+                (long long)r.n1, (long long)r.cut_mid, (long long)r.cut, (long long)kr.net_cut_best,
+                (long long)kr.iterations, (long long)kr.best_iter, secs(t0), base_name(o.input).c_str());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ek_cli_main(const char* tool_c, int argc, char** argv) {
@@ -315,6 +349,11 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.refine = true;
                 if (!std::isfinite(o.refine_eps) || o.refine_eps < 0) throw Fail{"--refine takes an imbalance >= 0"};
             } else if (a == "--refine-rounds") o.refine_rounds = std::stoi(need("--refine-rounds"));
+            else if (a == "--sweep") {
+                o.sweep_eps = std::stod(need("--sweep"));
+                o.sweep = true;
+                if (!std::isfinite(o.sweep_eps) || o.sweep_eps < 0) throw Fail{"--sweep takes an imbalance >= 0"};
+            } else if (a == "--sweep-ratio") o.sweep_ratio = true;
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -332,6 +371,10 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         }
     }
     try {
+        if ((o.sweep || o.sweep_ratio) && o.tool != "gKL2") {
+            std::printf("Usage: gKL2 <input_file> -EIG --sweep <imbalance> [--sweep-ratio]  (--sweep needs gKL2)\n");
+            return 1;
+        }
         if (o.tool == "cEIG") {
             mkdirs();  // cEIG.cpp:148-149
             if (pos.size() != 1) throw Fail{"Usage: ./EIG <input_file>"};
@@ -348,6 +391,14 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         if (o.refine && !o.kway) {
             std::printf("Usage: gKL2 <input_file> -EIG --k <parts> --refine <imbalance>  (--refine needs --k)\n");
             return 1;
+        }
+        if (o.sweep || o.sweep_ratio) {
+            if (!o.sweep || o.kway || o.tool != "gKL2" || !o.eig) {
+                std::printf("Usage: gKL2 <input_file> -EIG --sweep <imbalance> [--sweep-ratio]  (--sweep needs gKL2 and "
+                            "-EIG, and excludes --k; --sweep-ratio needs --sweep)\n");
+                return 1;
+            }
+            return run_sweep(o);
         }
         if (o.kway) {
             if (o.tool != "gKL2" || !o.eig) {

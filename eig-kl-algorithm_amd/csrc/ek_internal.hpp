@@ -183,6 +183,12 @@ struct RefineInput {
     std::vector<int32_t> pins, inc;
 };
 void refine_prepare(const ek_hgr& h, RefineInput& in);
+
+// sweep.cpp — what the host and the device sweep cut share: the argument
+// checks (EK_EINVAL as eigkl.h lists it; the opts with the defaults filled
+// in) and the balance window (n, max_part, s_lo, s_hi of the result)
+ek_sweep_opts sweep_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts);
+void sweep_window(int64_t n, double imbalance, ek_sweep_result& r);
 }  // namespace ek
 
 // ---------------------------------------------------------------------------
@@ -732,6 +738,33 @@ struct RefineDev {
 // slot (device, zero before the round): the round's candidates, independent
 // candidates, accepted moves and gain.  nets > 0.
 void refine_round(hipStream_t s, const RefineDev& d, unsigned long long* slot);
+
+// kernels_sweep.hip — the sweep cut (ek_sweep_cut): sort, profile, choice
+constexpr int SWEEP_TILE = 2048;                // keys per workgroup of a sort pass
+constexpr int SWEEP_SELECT_MAX_BLOCKS = 1024;   // partials of the choice
+int sweep_tiles(int n);
+// keys[i] = ord(v[i]), ids[i] = i; ghist (8 x 256 words, zero before): the
+// keys per digit of each of the 8 passes
+void sweep_keys(hipStream_t s, const double* v, int n, unsigned long long* keys, int32_t* ids, unsigned* ghist);
+// one stable pass on byte `pass` of the keys; table: 256 * sweep_tiles(n)
+// words, scan_tmp: sweep_scan_tmp_words of that
+void sweep_sort_pass(hipStream_t s, int n, int pass, const unsigned long long* keys_in, const int32_t* ids_in,
+                     unsigned long long* keys_out, int32_t* ids_out, unsigned* table, unsigned* scan_tmp);
+// pos[order[r]] = r
+void sweep_pos(hipStream_t s, const int32_t* order, int n, int32_t* pos);
+// prefix sum of data[0:count) in place, modulo 2^32 (exclusive or inclusive)
+size_t sweep_scan_tmp_words(long long count);
+void sweep_scan(hipStream_t s, unsigned* data, long long count, bool inclusive, unsigned* tmp);
+// diff (n + 1 words, zero before): +1 at lo + 1, -1 at hi + 1 of every net
+// with lo < hi; span_part[b]: those nets per workgroup, sweep_span_blocks(nets)
+int sweep_span_blocks(int64_t nets);
+void sweep_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* pos, int n,
+                 unsigned* diff, unsigned* span_part);
+// rec[0..3] = s*, profile[s*], profile[n / 2], sum of span_part[0:nspan);
+// part: 2 * sweep_select_blocks(window) words
+int sweep_select_blocks(int64_t window);
+void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, int64_t s_hi, int objective,
+                  unsigned* part, const unsigned* span_part, int nspan, long long* rec);
 
 }  // namespace dev
 }  // namespace ek

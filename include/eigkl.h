@@ -552,6 +552,65 @@ int ek_kway_refine(ek_ctx* ctx, const ek_hgr* h, const ek_kway_refine_opts* opts
                    int64_t* round_log, int64_t log_rounds, ek_kway_refine_result* result);
 
 /* ------------------------------------------------------------------ */
+/* Sweep cut of the Fiedler vector under a balance tolerance (Hagen-Kahng */
+/* EIG1's split).  No reference counterpart anywhere in this section: the  */
+/* reference splits at the median only (cEIG.cpp:204-209).                 */
+/* ------------------------------------------------------------------ */
+/* The rule, all integers, every tie broken by ids.  The n
+ * nodes of h (2 <= n <= INT32_MAX - 1) are sorted ascending by the key
+ * (ord(v[i]), i), ord as in ek_rank_split: order[r] is the node at rank r.
+ * Split s (0 <= s <= n) puts the s nodes of rank below s on side 1: the bits
+ * of ek_rank_split(v, s).  profile[s] = the nets with a pin on either side of
+ * split s = #{e : lo_e < s <= hi_e}, lo_e / hi_e the least / greatest rank of
+ * net e's pins (profile[0] = profile[n] = 0).  With L_max = floor((1 +
+ * imbalance) ceil(n / 2)) the window is s_lo = max(1, n - L_max) .. s_hi =
+ * min(n - 1, L_max); it always holds floor(n / 2).  The chosen s* is the
+ * window's least under: objective 0 (minimum cut) the lexicographic order of
+ * (profile[s], |2s - n|, s); objective 1 (ratio cut) a before b when
+ * profile[a] b (n - b) < profile[b] a (n - a), compared exactly, equal ratios
+ * by (|2s - n|, s).  Side 1 gets n1 = s* nodes, side 0 the other n0. */
+typedef struct {
+    int32_t objective; /* 0: minimum cut; 1: ratio cut c / (|A| |B|) */
+    int32_t pad;
+    double imbalance;  /* epsilon >= 0; default 0.03 */
+} ek_sweep_opts;
+
+typedef struct {
+    int64_t n, n0, n1;     /* nodes; side 0 and side 1 of the chosen split (n1 = s*) */
+    int64_t s_lo, s_hi;    /* the window */
+    int64_t max_part;      /* L_max */
+    int64_t cut;           /* profile[s*] */
+    int64_t cut_mid;       /* profile[floor(n / 2)] */
+    int64_t spanning_nets; /* nets with lo < hi */
+    double t_sort, t_profile, t_select; /* wall seconds (host clock) */
+} ek_sweep_result;
+
+/* objective 0, imbalance 0.03.  No reference counterpart. */
+void ek_sweep_default_opts(ek_sweep_opts* o);
+/* The sweep cut on the host (no GPU): the checker of ek_sweep_cut, single
+ * threaded and written from the rule.  v: n doubles (any bit patterns: ord is
+ * a total order).  order_out (n) and profile_out (n + 1) may be NULL.
+ * EK_EINVAL for n < 2, imbalance < 0 or not finite, an objective outside
+ * {0, 1}.  No reference counterpart. */
+int ek_sweep_cut_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opts, int32_t* order_out,
+                      int32_t* profile_out, ek_sweep_result* result);
+/* The same on the GPU, on an uploaded copy of v_host: the same order, profile
+ * and result integers.  The host reads back the result record, and order /
+ * profile only when asked for them.  The test seam of the kernels, as
+ * ek_rank_split_device is; every buffer is local to the call and the context
+ * keeps nothing.  No reference counterpart. */
+int ek_sweep_cut(ek_ctx* ctx, const ek_hgr* h, const double* v_host, const ek_sweep_opts* opts, int32_t* order_out,
+                 int32_t* profile_out, ek_sweep_result* result);
+/* The sweep cut of the Fiedler vector the last ek_lanczos_fiedler left on the
+ * device, then ek_kl_set_partition_fiedler_rank(ctx, result.n1): the context
+ * is in exactly the state that call leaves.  EK_ESTATE before
+ * ek_kl_graph_setup, without a Fiedler vector of the KL graph's size, or on a
+ * multi-rank context; EK_EINVAL when h's node count is not the KL graph's.
+ * result may be NULL.  No reference counterpart. */
+int ek_kl_set_partition_fiedler_sweep(ek_ctx* ctx, const ek_hgr* h, const ek_sweep_opts* opts,
+                                      ek_sweep_result* result);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
