@@ -339,8 +339,8 @@ __host__ __device__ inline int kl_sel_pad(int nck0, int nck1) {
 constexpr int KL_STAGE_ROW = KL_SEG_LANES + 1;
 constexpr int KL_STAGE_ROWS = 16;  // rows a gain wave stages per pass (16 coded, 8 plain)
 // updated rows that live in node1's / node2's own chunk, per list (more: the
-// chunk is rescanned).  A chunk holds 1024 of the list's positions, so most
-// swaps have none.
+// chunk is rescanned).  A chunk holds KL_CHUNK of the list's positions (2048;
+// KL_CHUNK_GB = 4096 in the GB form), so most swaps have none.
 constexpr int KL_AB_CAP = 16;
 // waves rescanning each of the two chunks node1 / node2 leave (E); the other
 // waves but the pair-gain one run the gain updates (A/B: EK_KL_EPARTS=1)

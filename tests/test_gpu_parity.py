@@ -176,7 +176,8 @@ def test_kl_random_init_synthetic(ek, oracle, ctx, mult, seed):
 
 
 @pytest.mark.parametrize("mode", ["EK_KL_GLOBAL_STATE", "EK_KL_NOSEG", "EK_KL_NOSEGC", "EK_KL_PIPE",
-                                  "EK_KL_PIPE+EK_KL_NOSEGC", "EK_KL_GBITS", "EK_KL_GBITS+EK_KL_NOSEGC"])
+                                  "EK_KL_PIPE+EK_KL_NOSEGC", "EK_KL_GBITS", "EK_KL_GBITS+EK_KL_NOSEGC",
+                                  "EK_KL_FIXLDS=0", "EK_KL_FIXLDS=0+EK_KL_NOSEGC"])
 @pytest.mark.parametrize("name", ["ibm01", "industry2"])
 def test_kl_fallback_paths_bitexact(ek, oracle, ctx, monkeypatch, name, mode):
     # the global-state loop (graphs whose on-chip state does not fit LDS), the
@@ -186,9 +187,11 @@ def test_kl_fallback_paths_bitexact(ek, oracle, ctx, monkeypatch, name, mode):
     # EK_KL_PIPE: the overlapped schedule (k_kl_swap_pipe, not the default:
     # profiles/r06/kl), coded and plain inline rows.  EK_KL_GBITS: the on-chip
     # loop with its side / locked bitmaps in global memory (the form graphs
-    # above ~500k nodes take), coded and plain inline rows
+    # above ~500k nodes take), coded and plain inline rows.  EK_KL_FIXLDS=0:
+    # the carved (not fixed) LDS layout, the default from 131,073 positions a list
     for m in mode.split("+"):
-        monkeypatch.setenv(m, "1")
+        name_, _, value = m.partition("=")
+        monkeypatch.setenv(name_, value or "1")
     h = ek.Hypergraph.read(circuit_path(name))
     _, _, _, _, o0, o1 = ek.eig_read(eig_path(name), h.nodes)
     ctx.kl_graph_setup(h.kl_graph())
