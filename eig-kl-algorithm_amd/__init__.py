@@ -130,6 +130,26 @@ class SweepResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _SWEEP_TIMES])
 
 
+FM_CHUNK = 256  # ek_internal.hpp FM_CHUNK: node ids per chunk key of the FM pass
+FM_LDS_CHUNKS = 2048  # ek_internal.hpp FM_LDS_CHUNKS: above this many chunks the keys live in global memory
+FM_THREADS = 512  # ek_internal.hpp FM_THREADS: the FM pass's one workgroup
+
+FM_MOVE_DTYPE = np.dtype([("node", "<i4"), ("gain", "<i4"), ("cut", "<i8")])  # eigkl.h ek_fm_move
+
+
+class FmOpts(_AbiStruct):
+    _fields_ = [("imbalance", ctypes.c_double), ("max_passes", _I32), ("stall", _I32)]
+
+
+_FM_TIMES = ("t_setup", "t_passes", "t_metrics")
+
+
+class FmResult(_AbiStruct):
+    _fields_ = ([("n", _I64), ("max_part", _I64), ("passes", _I32), ("passes_run", _I32)]
+                + [(k, _I64) for k in ("moves_tried", "moves_kept", "cut_before", "cut", "n0", "n1")]
+                + [(k, ctypes.c_double) for k in _FM_TIMES])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -238,6 +258,9 @@ _sig("ek_sweep_cut_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _
 _sig("ek_sweep_cut", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
 _sig("ek_kl_set_partition_fiedler_sweep", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts),
      ctypes.POINTER(SweepResult))
+_sig("ek_fm_default_opts", None, ctypes.POINTER(FmOpts))
+_sig("ek_fm_refine_host", ctypes.c_int, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64, ctypes.POINTER(FmResult))
+_sig("ek_fm_refine", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64, ctypes.POINTER(FmResult))
 
 lib = _lib
 
@@ -507,6 +530,39 @@ def sweep_cut_host(hgr, v, imbalance=0.03, ratio=False):
     host (ek_sweep_cut_host, the device path's checker): the minimum cut, or with ratio the ratio cut.
     Returns (result dict, order, profile): order[r] the node at rank r, profile[s] the nets cut by split s."""
     return _sweep_cut(lambda *a: _lib.ek_sweep_cut_host(hgr._h, *a), "sweep_cut_host", hgr, v, imbalance, ratio)
+
+
+def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap):
+    """(side, pass_log, move_log, result dict): pass_log has one row per pass run, the last uncounted one
+    included, (moves tried, t*, cut, |s0 - s1|); move_log (FM_MOVE_DTYPE) every move tried, in order."""
+    start = np.ascontiguousarray(side, np.uint8)
+    if len(start) != hgr.nodes:
+        raise ValueError(f"side has {len(start)} entries for {hgr.nodes} nodes")
+    o = FmOpts()
+    _lib.ek_fm_default_opts(ctypes.byref(o))
+    o.imbalance, o.max_passes, o.stall = float(imbalance), int(max_passes), int(stall)
+    pass_cap = 64
+    move_cap = max(1024, 4 * min(len(start), 1 << 20)) if move_cap is None else max(int(move_cap), 1)
+    while True:
+        out = start.copy()
+        plog = np.zeros((pass_cap, 4), np.int64)
+        mlog = np.zeros(move_cap, FM_MOVE_DTYPE)
+        r = FmResult()
+        _chk(call(ctypes.byref(o), _p(out), _p(plog), pass_cap, _p(mlog), move_cap, ctypes.byref(r)), what)
+        if r.passes_run <= pass_cap and r.moves_tried <= move_cap:
+            break  # (else: deterministic, so the same run again with room for its logs)
+        pass_cap, move_cap = max(pass_cap, r.passes_run), max(move_cap, r.moves_tried)
+    res = {name: getattr(r, name) for name, _ in FmResult._fields_}
+    return out, plog[:r.passes_run].copy(), mlog[:r.moves_tried].copy(), res
+
+
+def fm_refine_host(hgr, side, imbalance=0.03, max_passes=0, stall=1000, move_cap=None):
+    """Fiduccia-Mattheyses refinement of a bipartition on the integer net cut under L_max = floor((1 + imbalance)
+    ceil(n / 2)), on the host (ek_fm_refine_host, the device path's checker).  Returns (side, pass_log, move_log,
+    result dict).  move_cap: room for the move log (default 4 n); a run that tries more moves is run again with
+    room for them."""
+    return _fm_refine(lambda *a: _lib.ek_fm_refine_host(hgr._h, *a), "fm_refine_host", hgr, side, imbalance,
+                      max_passes, stall, move_cap)
 
 
 def eig_write(path, lam, median, bits, v):
@@ -787,6 +843,12 @@ class Context:
         r = KwayResult()
         _chk(_lib.ek_partition_kway(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)), "partition_kway")
         return part, _kway_result(r)
+
+    def fm_refine(self, hgr, side, imbalance=0.03, max_passes=0, stall=1000, move_cap=None):
+        """fm_refine_host on the GPU (ek_fm_refine): the same sides, logs and result integers.  Returns (side,
+        pass_log, move_log, result dict)."""
+        return _fm_refine(lambda *a: _lib.ek_fm_refine(self._c, hgr._h, *a), "fm_refine", hgr, side, imbalance,
+                          max_passes, stall, move_cap)
 
     def kway_refine(self, hgr, part, k, imbalance=0.03, max_rounds=0):
         """kway_refine_host on the GPU (ek_kway_refine): the same part vector, result integers and

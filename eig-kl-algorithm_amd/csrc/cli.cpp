@@ -39,6 +39,15 @@
 //                        "sweep:" is printed
 //   --sweep-ratio        with --sweep: the ratio cut c / (|A| |B|) instead of the
 //                        minimum cut
+//   --fm EPS             gKL2 <in.hgr> -EIG only, not with --k, alone or after
+//                        --sweep: the bipartition as without it, then the FM
+//                        refinement of the sides of KL's best prefix on the
+//                        device (ek_fm_refine) with imbalance EPS ->
+//                        results/<base>.part.2; one more line beginning "fm:"
+//   --fm-passes P        with --fm: at most P counted passes (default: until one
+//                        keeps nothing)
+//   --fm-stall S         with --fm: a pass ends S moves after its best prefix
+//                        (default 1000; 0: it runs until no node can move)
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -70,6 +79,11 @@ int kway_refine_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanc
 int sweep_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, int32_t limit, double imbalance,
                        int ratio, ek_sweep_result* sr, ek_kl_result* kr, double* lambda, ek_lanczos_stats* st)
     __attribute__((weak));
+// fm.cpp: the bipartition (the sweep's when asked for), then ek_fm_refine, for `--fm EPS`
+// (stall < 0: the default)
+int fm_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
+                    double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr, ek_fm_result* fr)
+    __attribute__((weak));
 }
 
 namespace {
@@ -84,6 +98,9 @@ struct Opts {
     int refine_rounds = 0;  // --refine-rounds R (0: no limit)
     bool sweep = false, sweep_ratio = false;  // --sweep EPS, --sweep-ratio
     double sweep_eps = 0.0;
+    bool fm = false, fm_sub = false;  // --fm EPS; --fm-passes or --fm-stall seen
+    double fm_eps = 0.0;
+    int fm_passes = 0, fm_stall = -1;  // (-1: the default)
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -312,6 +329,37 @@ int run_sweep(const Opts& o) {
     return 0;
 }
 
+constexpr const char* FM_USAGE =
+    "Usage: gKL2 <input_file> -EIG [--sweep <imbalance> [--sweep-ratio]] --fm <imbalance> [--fm-passes <P>] "
+    "[--fm-stall <S>]  (--fm needs gKL2 and -EIG, and excludes --k; --fm-passes and --fm-stall need --fm)\n";
+
+// gKL2 <in.hgr> -EIG [--sweep EPS] --fm EPS: the usual output (or the sweep's line), one line beginning "fm:",
+// results/<base>.part.2
+int run_fm(const Opts& o) {
+    const auto t0 = clk::now();
+    CtxInit ci(o.device, o.teardown);
+    ek_solve_opts so = solve_opts(o);
+    so.eig = 1;
+    if (!ek::fm_file_for_cli) throw Fail{"this build carries no FM refinement"};
+    ek_sweep_result sr{};
+    ek_kl_result kr{};
+    ek_fm_result fr{};
+    check(ek::fm_file_for_cli(ci.get(), o.input.c_str(), &so, o.sweep ? 1 : 0, o.sweep_eps, o.sweep_ratio ? 1 : 0, o.fm_eps,
+                              o.fm_passes, o.fm_stall, &sr, &kr, &fr), "FM refinement");
+    if (o.sweep)
+        std::printf("sweep: imbalance %g (%s), window %lld..%lld (max part %lld), n1 %lld, cut_mid %lld, cut %lld\n",
+                    o.sweep_eps, o.sweep_ratio ? "ratio cut" : "minimum cut", (long long)sr.s_lo, (long long)sr.s_hi,
+                    (long long)sr.max_part, (long long)sr.n1, (long long)sr.cut_mid, (long long)sr.cut);
+    std::printf("kl: net_cut_best %lld (%lld swaps, best prefix %lld)\n", (long long)kr.net_cut_best,
+                (long long)kr.iterations, (long long)kr.best_iter);
+    std::printf("fm: imbalance %g, cut_before %lld, cut %lld, passes %d, moves kept %lld / tried %lld, n0 %lld, n1 %lld, "
+                "max_part %lld, %.6f s (fm), %.3f s -> results/%s.part.2\n", o.fm_eps, (long long)fr.cut_before,
+                (long long)fr.cut, fr.passes, (long long)fr.moves_kept, (long long)fr.moves_tried, (long long)fr.n0,
+                (long long)fr.n1, (long long)fr.max_part, fr.t_setup + fr.t_passes + fr.t_metrics, secs(t0),
+                base_name(o.input).c_str());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ek_cli_main(const char* tool_c, int argc, char** argv) {
@@ -354,6 +402,18 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.sweep = true;
                 if (!std::isfinite(o.sweep_eps) || o.sweep_eps < 0) throw Fail{"--sweep takes an imbalance >= 0"};
             } else if (a == "--sweep-ratio") o.sweep_ratio = true;
+            else if (a == "--fm") {
+                o.fm_eps = std::stod(need("--fm"));
+                o.fm = true;
+                if (!std::isfinite(o.fm_eps) || o.fm_eps < 0) throw Fail{"--fm takes an imbalance >= 0"};
+            } else if (a == "--fm-passes") {
+                o.fm_passes = std::stoi(need("--fm-passes"));
+                o.fm_sub = true;
+            } else if (a == "--fm-stall") {
+                o.fm_stall = std::stoi(need("--fm-stall"));
+                o.fm_sub = true;
+                if (o.fm_stall < 0) throw Fail{"--fm-stall takes a move count >= 0"};
+            }
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -364,15 +424,21 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             else pos.push_back(a);
         } catch (const Fail& e) {
             std::fprintf(stderr, "Error: %s\n", e.msg.c_str());
+            if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
+            if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
             return 1;
         }
     }
     try {
         if ((o.sweep || o.sweep_ratio) && o.tool != "gKL2") {
             std::printf("Usage: gKL2 <input_file> -EIG --sweep <imbalance> [--sweep-ratio]  (--sweep needs gKL2)\n");
+            return 1;
+        }
+        if ((o.fm || o.fm_sub) && o.tool != "gKL2") {
+            std::printf("%s", FM_USAGE);
             return 1;
         }
         if (o.tool == "cEIG") {
@@ -391,6 +457,13 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         if (o.refine && !o.kway) {
             std::printf("Usage: gKL2 <input_file> -EIG --k <parts> --refine <imbalance>  (--refine needs --k)\n");
             return 1;
+        }
+        if (o.fm || o.fm_sub) {
+            if (!o.fm || o.kway || !o.eig || (o.sweep_ratio && !o.sweep)) {
+                std::printf("%s", FM_USAGE);
+                return 1;
+            }
+            return run_fm(o);
         }
         if (o.sweep || o.sweep_ratio) {
             if (!o.sweep || o.kway || o.tool != "gKL2" || !o.eig) {

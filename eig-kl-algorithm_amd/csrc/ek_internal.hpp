@@ -189,6 +189,11 @@ void refine_prepare(const ek_hgr& h, RefineInput& in);
 // in) and the balance window (n, max_part, s_lo, s_hi of the result)
 ek_sweep_opts sweep_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts);
 void sweep_window(int64_t n, double imbalance, ek_sweep_result& r);
+
+// fm.cpp — what the host and the device FM refinement share besides
+// refine_max_part and refine_prepare: the argument checks (EK_EINVAL as
+// eigkl.h lists it; the opts with the defaults filled in)
+ek_fm_opts fm_check(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side);
 }  // namespace ek
 
 // ---------------------------------------------------------------------------
@@ -765,6 +770,40 @@ void sweep_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int3
 int sweep_select_blocks(int64_t window);
 void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, int64_t s_hi, int objective,
                   unsigned* part, const unsigned* span_part, int nspan, long long* rec);
+
+// kernels_fm.hip — the FM refinement of a bipartition (ek_fm_refine)
+constexpr int FM_CHUNK = 256;        // node ids per chunk key
+constexpr int FM_THREADS = 512;      // the pass's one workgroup
+constexpr int FM_LDS_CHUNKS = 2048;  // up to this many chunks the keys live in LDS, above it in global memory
+struct FmDev {
+    int n, nets, nchunks, lmax;
+    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
+    const int32_t *pins, *inc;
+    unsigned *side, *lock;       // bitmaps, (n + 31) / 32 words; lock also holds the nodes of no net
+    const unsigned* lock0;       // the lock bitmap a pass starts from: the nodes of no net
+    int32_t* gain;               // n
+    unsigned* cnt;               // 2 a net: cnt(e, 0), cnt(e, 1)
+    long long* state;            // cut, s0, s1, and the counted cut of fm_counts (4 words)
+    int32_t* pass_nodes;         // the pass's moved nodes, in order (n)
+    ek_fm_move* mlog;            // the run's move log, mlog_cap entries (may be null)
+    long long mlog_cap;
+    unsigned long long* gkeys;   // 2 * nchunks chunk keys (nchunks > FM_LDS_CHUNKS only)
+    unsigned* gdirty;            // their dirty bitmap, (nchunks + 31) / 32 words, zero between launches
+    int32_t* gdlist;             // the dirty chunks' list, nchunks
+};
+// cnt(e, .) of the side bitmap, and state[3] (zero before) += the cut nets.  nets > 0.
+void fm_counts(hipStream_t s, const FmDev& d);
+// gain[v] = g(v) of every node from the incidence and the counts
+void fm_gains(hipStream_t s, const FmDev& d);
+// one pass from state[0..2] (the cut and the sides' sizes) and gain[]: moves
+// until none is left or the stall test ends it, each written to pass_nodes
+// and, at mlog_at + t, to mlog.  rec[0..3] = moves tried, t*, c and d of the
+// best prefix; state[0..2] = the cut and sizes of that prefix.  The sides,
+// counts and locks are left as after the last move: fm_rollback undoes the
+// moves past t*.  rec[0] = -1: a key named no node (state unchanged).
+void fm_pass(hipStream_t s, const FmDev& d, int stall, long long mlog_at, long long* rec);
+// moves first .. first + count - 1 of pass_nodes flipped back, the counts with them
+void fm_rollback(hipStream_t s, const FmDev& d, int first, int count);
 
 }  // namespace dev
 }  // namespace ek

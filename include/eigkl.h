@@ -611,6 +611,76 @@ int ek_kl_set_partition_fiedler_sweep(ek_ctx* ctx, const ek_hgr* h, const ek_swe
                                       ek_sweep_result* result);
 
 /* ------------------------------------------------------------------ */
+/* Fiduccia-Mattheyses refinement of a bipartition on the integer net    */
+/* cut, under a balance tolerance.  No reference counterpart anywhere in */
+/* this section: the reference's only refinement is the KL swap loop.    */
+/* ------------------------------------------------------------------ */
+/* The rule, all integers, every tie broken by sizes or ids.
+ * Only nets with at least 2 distinct pins take part; a node repeated inside a
+ * net counts once.  deg(v): those nets on v; a node of deg 0 never moves.
+ * cnt(e, s): the pins of e on side s; the cut is #{e : cnt(e, 0) > 0 and
+ * cnt(e, 1) > 0}.  L_max = floor((1 + imbalance) ceil(n / 2)).  For v on side
+ * a, g(v) = #{e on v : cnt(e, a) = 1} - #{e on v : cnt(e, 1 - a) = 0}, always
+ * of the current state: moving v lowers the cut by exactly g(v).
+ * One pass: (1) unlock every node; t = 0, c_0 = the cut, d_0 = |s_0 - s_1|
+ * (s: the sides' node counts).  (2) Side a has a candidate iff s[1 - a] <
+ * L_max and it holds an unlocked node of deg > 0: that side's unlocked node of
+ * greatest g, ties to the smaller id.  Of two candidates the one of greater g
+ * moves; equal g: the one whose side holds more nodes; equal sizes: the
+ * smaller id.  No candidate ends the pass.  (3) The node moves and is locked:
+ * t += 1, c_t = c_(t-1) - g, d_t = |s_0 - s_1|.  The best prefix t* is the
+ * least t that minimises (c_t, d_t) lexicographically.  (4) With stall > 0 the
+ * pass ends when t - t* >= stall.  (5) Moves t* + 1 .. t are undone.
+ * A pass counts iff t* > 0.  The run ends with the first pass of t* = 0, or
+ * after max_passes counted passes; (c, d) falls strictly with every counted
+ * pass.  A side already above L_max is not an error: it never receives.  With
+ * imbalance 0 and even n both sides are full when they are equal, and nothing
+ * moves: an FM pass needs slack (an odd n has one node of it). */
+typedef struct {
+    double imbalance;   /* epsilon >= 0; default 0.03 */
+    int32_t max_passes; /* <= 0: until a pass keeps nothing; default 0 */
+    int32_t stall;      /* <= 0: a pass runs until no node can move; default 1000,
+                         * a choice of the rule's parameter, not a measurement */
+} ek_fm_opts;
+
+typedef struct {
+    int32_t node; /* the node moved */
+    int32_t gain; /* its g when it moved */
+    int64_t cut;  /* the cut after the move */
+} ek_fm_move;
+
+typedef struct {
+    int64_t n, max_part;             /* nodes; L_max */
+    int32_t passes, passes_run;      /* counted passes (t* > 0); passes run (at most one more) */
+    int64_t moves_tried, moves_kept; /* sum of t and of t* over the passes run */
+    int64_t cut_before, cut;         /* the net cut of the sides given and of the sides returned */
+    int64_t n0, n1;                  /* the sides' node counts after the run */
+    double t_setup, t_passes, t_metrics; /* wall seconds (host clock) */
+} ek_fm_result;
+
+/* imbalance 0.03, max_passes 0, stall 1000. */
+void ek_fm_default_opts(ek_fm_opts* o);
+/* The refinement on the host (no GPU): the checker of ek_fm_refine, single
+ * threaded and written from the rule; after a move it recomputes the gains of
+ * the pins of the moved node's nets from their definition.  side_inout: one
+ * byte in {0, 1} per node of h, refined in place.  pass_log (may be NULL)
+ * receives four values per pass run, the last uncounted one included, for the
+ * first log_passes passes: moves tried, t*, the cut and |s_0 - s_1| after the
+ * rollback.  move_log (may be NULL) receives every move tried, in order, over
+ * all passes, the first move_cap of them.  EK_EINVAL for a side outside
+ * {0, 1}, imbalance < 0 or not finite, more than INT32_MAX - 1 nodes. */
+int ek_fm_refine_host(const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */, int64_t* pass_log,
+                      int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, ek_fm_result* result);
+/* The same on the GPU: the same bytes in side_inout, pass_log and move_log and
+ * the same result integers.  One persistent workgroup runs a pass in one
+ * launch; the host reads one 32-byte record per pass, and the move log and
+ * the sides once at the end.  EK_ESTATE on a multi-rank context.  Every
+ * buffer is local to the call and the context keeps nothing: any other call
+ * may follow. */
+int ek_fm_refine(ek_ctx* ctx, const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */,
+                 int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, ek_fm_result* result);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
