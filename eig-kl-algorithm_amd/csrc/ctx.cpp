@@ -678,6 +678,7 @@ void own_build_dev(ek_ctx* c, hipStream_t s, long long* tiles) {
     c->own_rowptr.ensure((nr + 1) * 4);
     c->own_col.ensure(size_t(std::max<long long>(tot, 1)) * 4);
     c->own_val.ensure(size_t(std::max<long long>(tot, 1)) * 8);
+    if (nr == 0) HIPCHK(hipMemsetAsync(c->own_rowptr.p, 0, 4, s));  // (own_split launches nothing: own_build_host's {0})
     ek::dev::own_split(s, (long long)nr, c->rowptr.as<int>(), c->col.as<int>(), c->val.as<double>(), lo, hi,
                        cnt.as<int>(), offs.as<long long>(), tiles, c->own_rowptr.as<int>(), c->own_col.as<int>(),
                        c->own_val.as<double>());
@@ -893,7 +894,7 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
     {
         Uploader up(c, s, (size_t(nets) + 1) * 8 + size_t(std::max<int64_t>(npins, 1)) * 4);
         up.put(c->lb_netptr, net_ptr, size_t(nets) + 1);
-        up.put(c->lb_pins, pins, size_t(std::max<int64_t>(npins, 1)));
+        up.put(c->lb_pins, pins, size_t(npins));  // (no pins: an allocation all the same, nothing read from `pins`)
     }
     pt.mark("pins staged");
     const size_t nr = size_t(nrows);
@@ -947,6 +948,13 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
     int cnt_h[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(cnt_h, b.counters, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    // k_rows counted the rows past the LDS sort: none of their lengths was
+    // written (the buffers come from hipMalloc as they are), so the host
+    // build is taken before the scan of b.len and k_row_write would read them
+    if (cnt_h[1] > 0) {
+        host_fallback("a row longer than the LDS sort");
+        return EK_OK;
+    }
     ek::dev::lap_long_rows(s, b, cnt_h[0]);
     ek::dev::exclusive_scan(s, b.len, int64_t(nr), c->lb_off.as<long long>(), tiles);
     // CSR on the device: rowptr (local), col, val; at most raw + nrows entries

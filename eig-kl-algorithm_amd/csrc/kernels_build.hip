@@ -195,10 +195,15 @@ __global__ __launch_bounds__(BT) void k_rows(long long nr, long long r0, const l
                                              const int64_t* __restrict__ net_ptr, const int32_t* __restrict__ pins,
                                              int* __restrict__ scol, double* __restrict__ sval, int* __restrict__ ulen,
                                              int* __restrict__ len, double* __restrict__ diag,
-                                             int* __restrict__ long_rows, int* __restrict__ n_long) {
+                                             int* __restrict__ long_rows, int* __restrict__ n_long,
+                                             int* __restrict__ too_long) {
     const long long i = (long long)blockIdx.x * BT + threadIdx.x;
     if (i >= nr) return;
     const long long at = rp[i];
+    if (rp[i + 1] - at > LONG_CAP) {  // past the LDS sort: counted here, so the host build is taken
+        atomicAdd(too_long, 1);       // before any kernel reads this row's (unwritten) lengths
+        return;
+    }
     if (rp[i + 1] - at > ROW_SHORT) {  // a workgroup of its own (k_rows_long)
         long_rows[atomicAdd(n_long, 1)] = int(i);
         return;
@@ -230,7 +235,7 @@ __global__ __launch_bounds__(BT) void k_rows_long(long long r0, const int* __res
     __shared__ int m_s;
     const long long i = long_rows[blockIdx.x];
     const long long at = rp[i];
-    if (rp[i + 1] - at > LONG_CAP) {
+    if (rp[i + 1] - at > LONG_CAP) {  // (k_rows lists no such row: the bound of key[] all the same)
         if (threadIdx.x == 0) atomicAdd(too_long, 1);
         return;
     }
@@ -413,17 +418,20 @@ void exclusive_scan(hipStream_t s, const int* in, long long n, long long* out, l
 }
 
 void lap_count(hipStream_t s, const LapBuild& b) {
-    hipLaunchKernelGGL(k_net_count, dim3(grid_of(b.nets)), dim3(BT), 0, s, b.nets, b.net_ptr, b.pins, b.r0, b.r1,
-                       b.icnt, b.rcnt);
+    if (b.nets > 0)
+        hipLaunchKernelGGL(k_net_count, dim3(grid_of(b.nets)), dim3(BT), 0, s, b.nets, b.net_ptr, b.pins, b.r0,
+                           b.r1, b.icnt, b.rcnt);
 }
 
 void lap_fill_rows(hipStream_t s, const LapBuild& b) {
     const long long nr = b.r1 - b.r0;
     int2* inc = reinterpret_cast<int2*>(b.inc);
-    hipLaunchKernelGGL(k_net_fill, dim3(grid_of(b.nets)), dim3(BT), 0, s, b.nets, b.net_ptr, b.pins, b.r0, b.r1, b.ip,
-                       b.cur, inc);
-    hipLaunchKernelGGL(k_rows, dim3(grid_of(nr)), dim3(BT), 0, s, nr, b.r0, b.ip, inc, b.rp, b.net_ptr, b.pins,
-                       b.scol, b.sval, b.ulen, b.len, b.diag, b.long_rows, b.counters);
+    if (b.nets > 0)
+        hipLaunchKernelGGL(k_net_fill, dim3(grid_of(b.nets)), dim3(BT), 0, s, b.nets, b.net_ptr, b.pins, b.r0, b.r1,
+                           b.ip, b.cur, inc);
+    if (nr > 0)
+        hipLaunchKernelGGL(k_rows, dim3(grid_of(nr)), dim3(BT), 0, s, nr, b.r0, b.ip, inc, b.rp, b.net_ptr, b.pins,
+                           b.scol, b.sval, b.ulen, b.len, b.diag, b.long_rows, b.counters, b.counters + 1);
 }
 
 void lap_long_rows(hipStream_t s, const LapBuild& b, int n_long) {
@@ -435,15 +443,19 @@ void lap_long_rows(hipStream_t s, const LapBuild& b, int n_long) {
 
 void lap_write(hipStream_t s, const LapBuild& b, const long long* off, int* rowptr, int* col, double* val) {
     const long long nr = b.r1 - b.r0;
-    hipLaunchKernelGGL(k_row_write, dim3(grid_of(nr)), dim3(BT), 0, s, nr, b.r0, b.rp, off, b.ulen, b.len, b.scol,
-                       b.sval, b.diag, rowptr, col, val);
+    if (nr > 0)
+        hipLaunchKernelGGL(k_row_write, dim3(grid_of(nr)), dim3(BT), 0, s, nr, b.r0, b.rp, off, b.ulen, b.len, b.scol,
+                           b.sval, b.diag, rowptr, col, val);
+    else  // a rank that owns no rows: the empty CSR the host build gives it
+        (void)hipMemsetAsync(rowptr, 0, sizeof(int), s);
 }
 
 void dict_build(hipStream_t s, long long nnz, const double* val, unsigned long long* table, int tsize,
                 int* overflow, int* flags, long long* code_of_slot, long long* tiles) {
     (void)hipMemsetAsync(table, 0xFF, size_t(tsize) * 8, s);
-    hipLaunchKernelGGL(k_dict_insert, dim3(grid_of(nnz)), dim3(BT), 0, s, nnz, val, table, unsigned(tsize - 1),
-                       overflow);
+    if (nnz > 0)
+        hipLaunchKernelGGL(k_dict_insert, dim3(grid_of(nnz)), dim3(BT), 0, s, nnz, val, table, unsigned(tsize - 1),
+                           overflow);
     hipLaunchKernelGGL(k_dict_flags, dim3(grid_of(tsize)), dim3(BT), 0, s, table, tsize, flags);
     exclusive_scan(s, flags, tsize, code_of_slot, tiles);  // code_of_slot[tsize] = number of distinct values
 }
