@@ -150,6 +150,14 @@ class FmResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _FM_TIMES])
 
 
+class FmWResult(_AbiStruct):
+    """eigkl.h ek_fm_w_result (the weighted FM refinement)."""
+    _fields_ = ([("n", _I64), ("total_weight", _I64), ("max_part", _I64), ("passes", _I32), ("passes_run", _I32)]
+                + [(k, _I64) for k in ("moves_tried", "moves_kept", "cut_before", "cut", "cut_nets_before", "cut_nets",
+                                       "w0", "w1", "n0", "n1")]
+                + [(k, ctypes.c_double) for k in _FM_TIMES])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -261,6 +269,15 @@ _sig("ek_kl_set_partition_fiedler_sweep", ctypes.c_int, _P, _P, ctypes.POINTER(S
 _sig("ek_fm_default_opts", None, ctypes.POINTER(FmOpts))
 _sig("ek_fm_refine_host", ctypes.c_int, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64, ctypes.POINTER(FmResult))
 _sig("ek_fm_refine", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64, ctypes.POINTER(FmResult))
+_sig("ek_hgr_set_weights", ctypes.c_int, _P, _P, _P)
+_sig("ek_hgr_weights", ctypes.c_int, _P, ctypes.POINTER(_I32), ctypes.POINTER(_I32))
+_sig("ek_hgr_copy_weights", ctypes.c_int, _P, _P, _P)
+_sig("ek_hgr_read_weighted", ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_P))
+_sig("ek_bipart_metrics_host", ctypes.c_int, _P, _P, _P)
+_sig("ek_fm_refine_w_host", ctypes.c_int, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64,
+     ctypes.POINTER(FmWResult))
+_sig("ek_fm_refine_w", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64,
+     ctypes.POINTER(FmWResult))
 
 lib = _lib
 
@@ -338,6 +355,37 @@ class Hypergraph:
         _chk(_lib.ek_hgr_from_pins(len(net_ptr) - 1, int(nodes), _p(net_ptr), _p(pins), ctypes.byref(h)),
              "from_pins")
         return cls(h)
+
+    @classmethod
+    def read_weighted(cls, path):
+        """The hMETIS reading of a .hgr file (ek_hgr_read_weighted): header `nets nodes [fmt]`, fmt 1 / 11 with a
+        weight at the head of every net line, fmt 10 / 11 with one node weight line per node, `%` comments."""
+        h = _P()
+        _chk(_lib.ek_hgr_read_weighted(os.fsencode(path), ctypes.byref(h)), f"read_weighted {path}")
+        return cls(h)
+
+    def set_weights(self, node_w=None, net_w=None):
+        """Node weights (>= 0, one per node) and net weights (>= 1, one per net); None clears that array, which
+        then stands for all ones (ek_hgr_set_weights).  Only the weighted FM refinement and bipart_metrics_host
+        read them."""
+        nets, nodes, _ = self.dims()
+        node_w = None if node_w is None else np.ascontiguousarray(node_w, np.int32)
+        net_w = None if net_w is None else np.ascontiguousarray(net_w, np.int32)
+        if node_w is not None and len(node_w) != nodes:
+            raise ValueError(f"node_w has {len(node_w)} entries for {nodes} nodes")
+        if net_w is not None and len(net_w) != nets:
+            raise ValueError(f"net_w has {len(net_w)} entries for {nets} nets")
+        _chk(_lib.ek_hgr_set_weights(self._h, _p(node_w), _p(net_w)), "set_weights")
+
+    def weights(self):
+        """(node_w, net_w): each an int32 array, or None for an array the hypergraph does not carry."""
+        nets, nodes, _ = self.dims()
+        hn, he = _I32(), _I32()
+        _chk(_lib.ek_hgr_weights(self._h, ctypes.byref(hn), ctypes.byref(he)), "weights")
+        node_w = np.empty(nodes, np.int32) if hn.value else None
+        net_w = np.empty(nets, np.int32) if he.value else None
+        _chk(_lib.ek_hgr_copy_weights(self._h, _p(node_w), _p(net_w)), "weights")
+        return node_w, net_w
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -532,9 +580,11 @@ def sweep_cut_host(hgr, v, imbalance=0.03, ratio=False):
     return _sweep_cut(lambda *a: _lib.ek_sweep_cut_host(hgr._h, *a), "sweep_cut_host", hgr, v, imbalance, ratio)
 
 
-def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap):
+def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap, result_type=None):
     """(side, pass_log, move_log, result dict): pass_log has one row per pass run, the last uncounted one
-    included, (moves tried, t*, cut, |s0 - s1|); move_log (FM_MOVE_DTYPE) every move tried, in order."""
+    included, (moves tried, t*, cut, |s0 - s1|); move_log (FM_MOVE_DTYPE) every move tried, in order.
+    result_type: the entry's result struct (FmResult by default, FmWResult for the weighted entries)."""
+    result_type = result_type or FmResult
     start = np.ascontiguousarray(side, np.uint8)
     if len(start) != hgr.nodes:
         raise ValueError(f"side has {len(start)} entries for {hgr.nodes} nodes")
@@ -547,12 +597,12 @@ def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap):
         out = start.copy()
         plog = np.zeros((pass_cap, 4), np.int64)
         mlog = np.zeros(move_cap, FM_MOVE_DTYPE)
-        r = FmResult()
+        r = result_type()
         _chk(call(ctypes.byref(o), _p(out), _p(plog), pass_cap, _p(mlog), move_cap, ctypes.byref(r)), what)
         if r.passes_run <= pass_cap and r.moves_tried <= move_cap:
             break  # (else: deterministic, so the same run again with room for its logs)
         pass_cap, move_cap = max(pass_cap, r.passes_run), max(move_cap, r.moves_tried)
-    res = {name: getattr(r, name) for name, _ in FmResult._fields_}
+    res = {name: getattr(r, name) for name, _ in result_type._fields_}
     return out, plog[:r.passes_run].copy(), mlog[:r.moves_tried].copy(), res
 
 
@@ -563,6 +613,25 @@ def fm_refine_host(hgr, side, imbalance=0.03, max_passes=0, stall=1000, move_cap
     room for them."""
     return _fm_refine(lambda *a: _lib.ek_fm_refine_host(hgr._h, *a), "fm_refine_host", hgr, side, imbalance,
                       max_passes, stall, move_cap)
+
+
+def bipart_metrics_host(hgr, side):
+    """(weighted cut, cut nets, W0, W1) of a side vector under hgr's weights, 1 where it carries none
+    (ek_bipart_metrics_host): only nets of at least 2 distinct pins count, a repeated pin once."""
+    side = np.ascontiguousarray(side, np.uint8)
+    if len(side) != hgr.nodes:
+        raise ValueError(f"side has {len(side)} entries for {hgr.nodes} nodes")
+    out = np.zeros(4, np.int64)
+    _chk(_lib.ek_bipart_metrics_host(hgr._h, _p(side), _p(out)), "bipart_metrics_host")
+    return tuple(int(x) for x in out)
+
+
+def fm_refine_w_host(hgr, side, imbalance=0.03, max_passes=0, stall=1000, move_cap=None):
+    """fm_refine_host under hgr's node and net weights (ek_fm_refine_w_host, the checker of Context.fm_refine_w):
+    the weighted cut, L_max = floor((1 + imbalance) ceil(W / 2)) on the sides' weights.  Returns (side, pass_log,
+    move_log, result dict): a move's gain and cut are weighted, a pass_log row ends with |S0 - S1|."""
+    return _fm_refine(lambda *a: _lib.ek_fm_refine_w_host(hgr._h, *a), "fm_refine_w_host", hgr, side, imbalance,
+                      max_passes, stall, move_cap, FmWResult)
 
 
 def eig_write(path, lam, median, bits, v):
@@ -849,6 +918,12 @@ class Context:
         pass_log, move_log, result dict)."""
         return _fm_refine(lambda *a: _lib.ek_fm_refine(self._c, hgr._h, *a), "fm_refine", hgr, side, imbalance,
                           max_passes, stall, move_cap)
+
+    def fm_refine_w(self, hgr, side, imbalance=0.03, max_passes=0, stall=1000, move_cap=None):
+        """fm_refine_w_host on the GPU (ek_fm_refine_w): the same sides, logs and result integers.  Returns (side,
+        pass_log, move_log, result dict)."""
+        return _fm_refine(lambda *a: _lib.ek_fm_refine_w(self._c, hgr._h, *a), "fm_refine_w", hgr, side, imbalance,
+                          max_passes, stall, move_cap, FmWResult)
 
     def kway_refine(self, hgr, part, k, imbalance=0.03, max_rounds=0):
         """kway_refine_host on the GPU (ek_kway_refine): the same part vector, result integers and

@@ -48,6 +48,12 @@
 //                        keeps nothing)
 //   --fm-stall S         with --fm: a pass ends S moves after its best prefix
 //                        (default 1000; 0: it runs until no node can move)
+//   --weighted           with --fm: the file is read as hMETIS reads it
+//                        (ek_hgr_read_weighted: fmt 0, 1, 10 or 11, '%' comments)
+//                        and the refinement is the weighted one (ek_fm_refine_w):
+//                        node weights under the bound, net weights in the cut.
+//                        Lanczos, the split and KL ignore the weights.  The line
+//                        printed begins "fmw:" instead of "fm:"
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -84,6 +90,10 @@ int sweep_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lan
 int fm_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
                     double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr, ek_fm_result* fr)
     __attribute__((weak));
+// fmw.cpp: the same on the hMETIS reading of the file, with ek_fm_refine_w, for `--fm EPS --weighted`
+int fmw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
+                     double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr,
+                     ek_fm_w_result* fr) __attribute__((weak));
 }
 
 namespace {
@@ -101,6 +111,7 @@ struct Opts {
     bool fm = false, fm_sub = false;  // --fm EPS; --fm-passes or --fm-stall seen
     double fm_eps = 0.0;
     int fm_passes = 0, fm_stall = -1;  // (-1: the default)
+    bool weighted = false;             // --weighted
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -332,6 +343,10 @@ int run_sweep(const Opts& o) {
 constexpr const char* FM_USAGE =
     "Usage: gKL2 <input_file> -EIG [--sweep <imbalance> [--sweep-ratio]] --fm <imbalance> [--fm-passes <P>] "
     "[--fm-stall <S>]  (--fm needs gKL2 and -EIG, and excludes --k; --fm-passes and --fm-stall need --fm)\n";
+constexpr const char* FMW_USAGE =
+    "Usage: gKL2 <input_file> -EIG [--sweep <imbalance> [--sweep-ratio]] --fm <imbalance> --weighted [--fm-passes <P>] "
+    "[--fm-stall <S>]  (--weighted needs --fm and excludes --k; the file is read as hMETIS reads it, fmt 0, 1, 10 or "
+    "11; the FM refinement weighs nodes and nets, while Lanczos, the split and KL ignore the weights)\n";
 
 // gKL2 <in.hgr> -EIG [--sweep EPS] --fm EPS: the usual output (or the sweep's line), one line beginning "fm:",
 // results/<base>.part.2
@@ -344,14 +359,32 @@ int run_fm(const Opts& o) {
     ek_sweep_result sr{};
     ek_kl_result kr{};
     ek_fm_result fr{};
+    auto print_sweep_and_kl = [&] {
+        if (o.sweep)
+            std::printf("sweep: imbalance %g (%s), window %lld..%lld (max part %lld), n1 %lld, cut_mid %lld, cut %lld\n",
+                        o.sweep_eps, o.sweep_ratio ? "ratio cut" : "minimum cut", (long long)sr.s_lo, (long long)sr.s_hi,
+                        (long long)sr.max_part, (long long)sr.n1, (long long)sr.cut_mid, (long long)sr.cut);
+        std::printf("kl: net_cut_best %lld (%lld swaps, best prefix %lld)\n", (long long)kr.net_cut_best,
+                    (long long)kr.iterations, (long long)kr.best_iter);
+    };
+    if (o.weighted) {
+        if (!ek::fmw_file_for_cli) throw Fail{"this build carries no weighted FM refinement"};
+        ek_fm_w_result wr{};
+        check(ek::fmw_file_for_cli(ci.get(), o.input.c_str(), &so, o.sweep ? 1 : 0, o.sweep_eps, o.sweep_ratio ? 1 : 0,
+                                   o.fm_eps, o.fm_passes, o.fm_stall, &sr, &kr, &wr), "weighted FM refinement");
+        print_sweep_and_kl();
+        std::printf("fmw: imbalance %g, cut_before %lld, cut %lld, cut_nets_before %lld, cut_nets %lld, passes %d, moves "
+                    "kept %lld / tried %lld, w0 %lld, w1 %lld, total_weight %lld, max_part %lld, n0 %lld, n1 %lld, %.6f s "
+                    "(fmw), %.3f s -> results/%s.part.2\n", o.fm_eps, (long long)wr.cut_before, (long long)wr.cut,
+                    (long long)wr.cut_nets_before, (long long)wr.cut_nets, wr.passes, (long long)wr.moves_kept,
+                    (long long)wr.moves_tried, (long long)wr.w0, (long long)wr.w1, (long long)wr.total_weight,
+                    (long long)wr.max_part, (long long)wr.n0, (long long)wr.n1, wr.t_setup + wr.t_passes + wr.t_metrics,
+                    secs(t0), base_name(o.input).c_str());
+        return 0;
+    }
     check(ek::fm_file_for_cli(ci.get(), o.input.c_str(), &so, o.sweep ? 1 : 0, o.sweep_eps, o.sweep_ratio ? 1 : 0, o.fm_eps,
                               o.fm_passes, o.fm_stall, &sr, &kr, &fr), "FM refinement");
-    if (o.sweep)
-        std::printf("sweep: imbalance %g (%s), window %lld..%lld (max part %lld), n1 %lld, cut_mid %lld, cut %lld\n",
-                    o.sweep_eps, o.sweep_ratio ? "ratio cut" : "minimum cut", (long long)sr.s_lo, (long long)sr.s_hi,
-                    (long long)sr.max_part, (long long)sr.n1, (long long)sr.cut_mid, (long long)sr.cut);
-    std::printf("kl: net_cut_best %lld (%lld swaps, best prefix %lld)\n", (long long)kr.net_cut_best,
-                (long long)kr.iterations, (long long)kr.best_iter);
+    print_sweep_and_kl();
     std::printf("fm: imbalance %g, cut_before %lld, cut %lld, passes %d, moves kept %lld / tried %lld, n0 %lld, n1 %lld, "
                 "max_part %lld, %.6f s (fm), %.3f s -> results/%s.part.2\n", o.fm_eps, (long long)fr.cut_before,
                 (long long)fr.cut, fr.passes, (long long)fr.moves_kept, (long long)fr.moves_tried, (long long)fr.n0,
@@ -414,6 +447,7 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.fm_sub = true;
                 if (o.fm_stall < 0) throw Fail{"--fm-stall takes a move count >= 0"};
             }
+            else if (a == "--weighted") o.weighted = true;
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -435,6 +469,10 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
     try {
         if ((o.sweep || o.sweep_ratio) && o.tool != "gKL2") {
             std::printf("Usage: gKL2 <input_file> -EIG --sweep <imbalance> [--sweep-ratio]  (--sweep needs gKL2)\n");
+            return 1;
+        }
+        if (o.weighted && (!o.fm || o.kway || o.tool != "gKL2")) {
+            std::printf("%s", FMW_USAGE);
             return 1;
         }
         if ((o.fm || o.fm_sub) && o.tool != "gKL2") {

@@ -89,6 +89,9 @@ struct ek_hgr {
     // sum over nets of k (k - 1), k >= 2 pins (the clique expansion's raw
     // entries), when the reader counted it; -1: not known
     int64_t raw_pairs = -1;
+    // optional weights (ek_hgr_set_weights, ek_hgr_read_weighted); empty: every
+    // weight is 1.  node_w: nodes values >= 0; net_w: nets values >= 1
+    std::vector<int32_t> node_w, net_w;
 };
 namespace ek {
 // ek_spmv_setup_pins for an ek_hgr (ctx.cpp): its pins need no range scan
@@ -194,6 +197,18 @@ void sweep_window(int64_t n, double imbalance, ek_sweep_result& r);
 // refine_max_part and refine_prepare: the argument checks (EK_EINVAL as
 // eigkl.h lists it; the opts with the defaults filled in)
 ek_fm_opts fm_check(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side);
+
+// fmw.cpp — what the host and the device weighted FM refinement share: the
+// input.  fm_check, then refine_prepare with c(e) of every participating net
+// and w(v) of every node (1 where h has no such array), W, L_max = floor((1 +
+// imbalance) ceil(W / 2)) and the range rules of eigkl.h (EK_EINVAL)
+struct FmwInput {
+    RefineInput in;
+    std::vector<int32_t> cw, w;  // per participating net; per node
+    int64_t total = 0, max_part = 0;
+    ek_fm_opts opts;
+};
+void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side, FmwInput& out);
 }  // namespace ek
 
 // ---------------------------------------------------------------------------
@@ -804,6 +819,40 @@ void fm_gains(hipStream_t s, const FmDev& d);
 void fm_pass(hipStream_t s, const FmDev& d, int stall, long long mlog_at, long long* rec);
 // moves first .. first + count - 1 of pass_nodes flipped back, the counts with them
 void fm_rollback(hipStream_t s, const FmDev& d, int first, int count);
+
+// kernels_fmw.hip — the weighted FM refinement (ek_fm_refine_w): FmDev's
+// layout with the weights, 64-bit side weights and a 64-bit L_max.  The chunk
+// size, the workgroup and the LDS threshold are the unweighted pass's.
+struct FmwDev {
+    int n, nets, nchunks;
+    long long lmax;
+    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
+    const int32_t *pins, *inc;
+    const int32_t *cw, *w;       // c(e) per net, w(v) per node
+    unsigned *side, *lock;       // bitmaps, (n + 31) / 32 words; lock also holds the nodes of no net
+    const unsigned* lock0;       // the lock bitmap a pass starts from: the nodes of no net
+    int32_t* gain;               // n
+    unsigned* cnt;               // 2 a net: cnt(e, 0), cnt(e, 1)
+    long long* state;            // weighted cut, S0, S1, and fmw_counts' weighted cut and cut nets (5 words)
+    int32_t* pass_nodes;         // the pass's moved nodes, in order (n)
+    ek_fm_move* mlog;            // the run's move log, mlog_cap entries (may be null)
+    long long mlog_cap;
+    unsigned long long* gkeys;   // 2 * nchunks chunk keys (nchunks > FM_LDS_CHUNKS only)
+    unsigned* gdirty;            // their dirty bitmap, (nchunks + 31) / 32 words, zero between launches
+    int32_t* gdlist;             // the dirty chunks' list, nchunks
+};
+// cnt(e, .) of the side bitmap; state[3] += the weighted cut, state[4] += the cut nets (zero before).  nets > 0.
+void fmw_counts(hipStream_t s, const FmwDev& d);
+// gain[v] = the weighted g(v) of every node from the incidence, the counts and c(e)
+void fmw_gains(hipStream_t s, const FmwDev& d);
+// one pass from state[0..2] (the weighted cut and the sides' weights) and
+// gain[], as fm_pass.  rec[0..3] = moves tried, t*, c and d of the best
+// prefix; state[0] = c, state[1..2] = the sides' weights after the LAST move:
+// fmw_rollback undoes the moves past t*, the weights included.  rec[0] = -1: a
+// key named no node (state unchanged).
+void fmw_pass(hipStream_t s, const FmwDev& d, int stall, long long mlog_at, long long* rec);
+// moves first .. first + count - 1 of pass_nodes flipped back, the counts and state[1..2] with them
+void fmw_rollback(hipStream_t s, const FmwDev& d, int first, int count);
 
 }  // namespace dev
 }  // namespace ek

@@ -384,8 +384,14 @@ int ek_hgr_largest_component(const ek_hgr* h, ek_hgr** out, int32_t* node_map) {
         if (p1 == p0 || nid[size_t(h->pins[size_t(p0)])] < 0) continue;  // every pin of a kept net is kept
         for (int64_t p = p0; p < p1; ++p) c->pins.push_back(nid[size_t(h->pins[size_t(p)])]);
         c->net_ptr.push_back(int64_t(c->pins.size()));
+        if (!h->net_w.empty()) c->net_w.push_back(h->net_w[size_t(e)]);
     }
     c->nets = int64_t(c->net_ptr.size()) - 1;
+    if (!h->node_w.empty()) {
+        c->node_w.resize(size_t(m));
+        for (int64_t i = 0; i < n; ++i)
+            if (nid[size_t(i)] >= 0) c->node_w[size_t(nid[size_t(i)])] = h->node_w[size_t(i)];
+    }
     if (node_map) std::copy(nid.begin(), nid.end(), node_map);
     *out = c.release();
     return EK_OK;
@@ -430,10 +436,17 @@ int ek_hgr_induce(const ek_hgr* h, const uint8_t* keep, ek_hgr** out, int32_t* n
     c->net_ptr.resize(size_t(c->nets) + 1);
     c->pins.resize(size_t(cp[size_t(T)]));
     c->net_ptr[0] = 0;
+    if (!h->net_w.empty()) c->net_w.resize(size_t(c->nets));
+    if (!h->node_w.empty()) {
+        c->node_w.resize(size_t(m));
+        for (int64_t i = 0; i < n; ++i)
+            if (nid[size_t(i)] >= 0) c->node_w[size_t(nid[size_t(i)])] = h->node_w[size_t(i)];
+    }
     ek::run_threads(T, [&](int t) {
         int64_t a = cn[size_t(t)], b = cp[size_t(t)];
         for (int64_t e = nets * t / T; e < nets * (t + 1) / T; ++e) {
             if (kept_pins(e) < 2) continue;
+            if (!h->net_w.empty()) c->net_w[size_t(a)] = h->net_w[size_t(e)];
             for (int64_t p = h->net_ptr[size_t(e)]; p < h->net_ptr[size_t(e) + 1]; ++p) {
                 const int32_t v = nid[size_t(h->pins[size_t(p)])];
                 if (v >= 0) c->pins[size_t(b++)] = v;
@@ -454,19 +467,152 @@ int ek_hgr_write(const ek_hgr* h, const char* path) {
     if (!f) ek::fail(EK_EIO, "cannot write %s: %s", path, std::strerror(errno));
     std::string out;
     out.reserve(size_t(h->pins.size()) * 8 + 64);
-    out += std::to_string(h->nets) + " " + std::to_string(h->nodes) + "\n";
+    // the hMETIS fmt of a weighted hypergraph: 1 net weights, 10 node weights, 11 both
+    const int fmt = (h->net_w.empty() ? 0 : 1) + (h->node_w.empty() ? 0 : 10);
+    out += std::to_string(h->nets) + " " + std::to_string(h->nodes) + (fmt ? " " + std::to_string(fmt) : "") + "\n";
     char tmp[16];
     for (int64_t e = 0; e < h->nets; ++e) {
+        if (fmt & 1) out += std::to_string(h->net_w[size_t(e)]);
         for (int64_t p = h->net_ptr[size_t(e)]; p < h->net_ptr[size_t(e) + 1]; ++p) {
-            if (p != h->net_ptr[size_t(e)]) out += ' ';
+            if ((fmt & 1) || p != h->net_ptr[size_t(e)]) out += ' ';
             const int len = snprintf(tmp, sizeof tmp, "%d", h->pins[size_t(p)] + 1);
             out.append(tmp, size_t(len));
         }
         out += '\n';
     }
+    for (int32_t w : h->node_w) out += std::to_string(w) + "\n";
     const size_t wr = std::fwrite(out.data(), 1, out.size(), f);
     std::fclose(f);
     if (wr != out.size()) ek::fail(EK_EIO, "short write to %s", path);
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_hgr_set_weights(ek_hgr* h, const int32_t* node_w, const int32_t* net_w) {
+    EK_TRY
+    if (!h) ek::fail(EK_EINVAL, "ek_hgr_set_weights: null handle");
+    for (int64_t i = 0; node_w && i < h->nodes; ++i)
+        if (node_w[i] < 0) ek::fail(EK_EINVAL, "ek_hgr_set_weights: weight %d of node %lld (>= 0)", node_w[i], (long long)i);
+    for (int64_t e = 0; net_w && e < h->nets; ++e)
+        if (net_w[e] < 1) ek::fail(EK_EINVAL, "ek_hgr_set_weights: weight %d of net %lld (>= 1)", net_w[e], (long long)e);
+    if (node_w) h->node_w.assign(node_w, node_w + h->nodes);
+    else h->node_w.clear();
+    if (net_w) h->net_w.assign(net_w, net_w + h->nets);
+    else h->net_w.clear();
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_hgr_weights(const ek_hgr* h, int32_t* has_node_w, int32_t* has_net_w) {
+    if (!h) {
+        ek::set_error("ek_hgr_weights: null handle");
+        return EK_EINVAL;
+    }
+    // (an array over no node or no net cannot be told from an absent one: both stand for all ones)
+    if (has_node_w) *has_node_w = !h->node_w.empty();
+    if (has_net_w) *has_net_w = !h->net_w.empty();
+    return EK_OK;
+}
+
+int ek_hgr_copy_weights(const ek_hgr* h, int32_t* node_w_out, int32_t* net_w_out) {
+    if (!h) {
+        ek::set_error("ek_hgr_copy_weights: null handle");
+        return EK_EINVAL;
+    }
+    if (node_w_out) {
+        if (h->node_w.empty()) std::fill(node_w_out, node_w_out + h->nodes, 1);
+        else std::copy(h->node_w.begin(), h->node_w.end(), node_w_out);
+    }
+    if (net_w_out) {
+        if (h->net_w.empty()) std::fill(net_w_out, net_w_out + h->nets, 1);
+        else std::copy(h->net_w.begin(), h->net_w.end(), net_w_out);
+    }
+    return EK_OK;
+}
+
+// The hMETIS reading (eigkl.h): one thread, one pass over the lines.  Every
+// token must be an unsigned integer, which is what rejects a negative weight.
+int ek_hgr_read_weighted(const char* path, ek_hgr** out) {
+    EK_TRY
+    if (!path || !out) ek::fail(EK_EINVAL, "ek_hgr_read_weighted: null argument");
+    ek::dvec<char> buf;
+    slurp(path, buf);
+    const char* p = buf.empty() ? "" : buf.data();
+    const char* const end = p + buf.size();
+    int64_t line_no = 0;
+    std::vector<uint64_t> tok;
+    // the next line that is no comment into tok; false at the end of the file
+    auto next_line = [&]() {
+        for (;;) {
+            if (p >= end) return false;
+            const char* nl = static_cast<const char*>(std::memchr(p, '\n', size_t(end - p)));
+            const char* q = p;
+            const char* const le = nl ? nl : end;
+            p = nl ? nl + 1 : end;
+            ++line_no;
+            if (q < le && *q == '%') continue;
+            tok.clear();
+            while (q < le) {
+                while (q < le && is_space(*q)) ++q;
+                if (q >= le) break;
+                uint64_t v = 0;
+                const char* const t0 = q;
+                while (q < le && *q >= '0' && *q <= '9') {
+                    v = v * 10 + uint64_t(*q - '0');
+                    if (v > 0xffffffffull) ek::fail(EK_EINVAL, "%s:%lld: a number above 2^32", path, (long long)line_no);
+                    ++q;
+                }
+                if (q == t0 || (q < le && !is_space(*q)))
+                    ek::fail(EK_EINVAL, "%s:%lld: a token that is no unsigned integer", path, (long long)line_no);
+                tok.push_back(v);
+            }
+            return true;
+        }
+    };
+    if (!next_line() || tok.size() < 2 || tok.size() > 3)
+        ek::fail(EK_EINVAL, "%s: header must be '<nets> <nodes> [fmt]'", path);
+    const uint64_t fmt = tok.size() == 3 ? tok[2] : 0;
+    if (fmt != 0 && fmt != 1 && fmt != 10 && fmt != 11) ek::fail(EK_EINVAL, "%s: fmt %llu (0, 1, 10 or 11)", path, (unsigned long long)fmt);
+    const bool has_net_w = fmt == 1 || fmt == 11, has_node_w = fmt >= 10;
+    auto h = std::make_unique<ek_hgr>();
+    h->nets = int64_t(tok[0]);
+    h->nodes = int64_t(tok[1]);
+    if (h->nodes > INT32_MAX || h->nets > INT32_MAX) ek::fail(EK_EINVAL, "%s: sizes exceed int32", path);
+    h->net_ptr.assign(size_t(h->nets) + 1, 0);
+    if (has_net_w) h->net_w.resize(size_t(h->nets));
+    int64_t pairs = 0;
+    for (int64_t e = 0; e < h->nets; ++e) {
+        if (!next_line()) tok.clear();  // (a missing line: an empty net, as in ek_hgr_read)
+        size_t first = 0;
+        if (has_net_w) {
+            if (tok.empty()) ek::fail(EK_EINVAL, "%s: net %lld has no weight", path, (long long)e + 1);
+            if (tok[0] < 1 || tok[0] > uint64_t(INT32_MAX))
+                ek::fail(EK_EINVAL, "%s:%lld: net weight %llu outside [1, 2^31 - 1]", path, (long long)line_no,
+                         (unsigned long long)tok[0]);
+            h->net_w[size_t(e)] = int32_t(tok[0]);
+            first = 1;
+        }
+        for (size_t j = first; j < tok.size(); ++j) {
+            if (tok[j] < 1 || int64_t(tok[j]) > h->nodes)
+                ek::fail(EK_EINVAL, "%s:%lld: pin id %llu outside [1, %lld]", path, (long long)line_no,
+                         (unsigned long long)tok[j], (long long)h->nodes);
+            h->pins.push_back(int32_t(tok[j]) - 1);
+        }
+        const int64_t k = int64_t(tok.size() - first);
+        pairs += k >= 2 ? k * (k - 1) : 0;
+        h->net_ptr[size_t(e) + 1] = int64_t(h->pins.size());
+    }
+    h->raw_pairs = pairs;
+    if (has_node_w) {
+        h->node_w.resize(size_t(h->nodes));
+        for (int64_t v = 0; v < h->nodes; ++v) {
+            if (!next_line()) ek::fail(EK_EINVAL, "%s: %lld node weight lines of %lld", path, (long long)v, (long long)h->nodes);
+            if (tok.size() != 1 || tok[0] > uint64_t(INT32_MAX))
+                ek::fail(EK_EINVAL, "%s:%lld: a node weight line holds one weight in [0, 2^31 - 1]", path, (long long)line_no);
+            h->node_w[size_t(v)] = int32_t(tok[0]);
+        }
+    }
+    *out = h.release();
     return EK_OK;
     EK_CATCH
 }

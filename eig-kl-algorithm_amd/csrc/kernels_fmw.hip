@@ -1,0 +1,429 @@
+// The weighted Fiduccia-Mattheyses refinement (ctx_fmw.cpp; the rule: eigkl.h,
+// DESIGN.md §12): kernels_fm.hip's four kernels with c(e) in the gains and the
+// cut, w(v) in the fit test and 64-bit side weights.  A translation unit of
+// its own, beside the unweighted one: neither that file nor its code objects
+// change, which is why the few device helpers below are stated again here
+// instead of being moved out of it.
+//
+// As there, everything is integer work and no result depends on the order
+// waves or atomics arrive in: the atomics are integer adds (gains by +-c(e),
+// counts, the sides' weights in the rollback), bit sets / clears of distinct
+// bits, and a list of dirty chunks whose order does not matter.  k_fmw_pass
+// waits on nothing outside its one workgroup, and its loop runs at most once
+// per node.  State a pass changes is read and written with relaxed agent-scope
+// atomics; the weights (cw, w) and the structure are never written on the
+// device and are read with plain loads.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "ek_internal.hpp"
+
+namespace ek {
+namespace dev {
+
+namespace {
+
+using u64 = unsigned long long;
+
+template <class T>
+__device__ __forceinline__ T ld(const T* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <class T>
+__device__ __forceinline__ void st(T* p, T v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned bit_of(const unsigned* words, unsigned v) { return (ld(words + (v >> 5)) >> (v & 31u)) & 1u; }
+
+__device__ __forceinline__ u64 wave_max(u64 k) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 x = __shfl_xor(k, o, 64);
+        k = x > k ? x : k;
+    }
+    return k;
+}
+template <class T>
+__device__ __forceinline__ T wave_sum(T x) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// the barrier between two phases of the pass: this wave's stores and atomics
+// have reached L2 (vmcnt(0), gfx9 encoding) before any wave goes on to read them
+__device__ __forceinline__ void wg_barrier() {
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+}
+
+constexpr int FC_THREADS = 256, FC_SHORT = 8;  // a thread takes a net of <= FC_SHORT pins, the wave a longer one
+constexpr int FG_LONG = 32;                    // a thread takes a node of <= FG_LONG nets, the wave one of more
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// cnt(e, 0), cnt(e, 1) of every net, laid out as k_fm_counts.  state[3] += the
+// block's weighted cut, state[4] += its cut nets: a 64-bit sum over the block.
+__global__ __launch_bounds__(FC_THREADS) void k_fmw_counts(FmwDev d) {
+    __shared__ u64 ws[FC_THREADS / 64];
+    __shared__ unsigned wn[FC_THREADS / 64];
+    const int t = threadIdx.x, l = t & 63;
+    const long long e = blockIdx.x * (long long)FC_THREADS + t;
+    u64 cutw = 0ull;    // this thread's cut nets' weight (lane 0: also the wave's long nets')
+    unsigned cut = 0u;  // and their number
+    int64_t p0 = 0, p1 = 0;
+    if (e < d.nets) {
+        p0 = d.net_ptr[e];
+        p1 = d.net_ptr[e + 1];
+    }
+    const bool is_long = p1 - p0 > FC_SHORT;
+    if (e < d.nets && !is_long) {
+        unsigned c1 = 0u;
+        for (int64_t p = p0; p < p1; ++p) c1 += bit_of(d.side, unsigned(d.pins[p]));
+        const unsigned c0 = unsigned(p1 - p0) - c1;
+        d.cnt[2 * e] = c0;
+        d.cnt[2 * e + 1] = c1;
+        if (c0 > 0u && c1 > 0u) {
+            cutw += u64(d.cw[e]);
+            ++cut;
+        }
+    }
+    u64 todo = __ballot(is_long);
+    while (todo) {  // the wave's long nets, one after the other (the ballot is wave-uniform)
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1ull;
+        const int64_t q0 = __shfl(p0, src, 64), q1 = __shfl(p1, src, 64);
+        const long long f = e - l + src;
+        unsigned c1 = 0u;
+        for (int64_t p = q0 + l; p < q1; p += 64) c1 += bit_of(d.side, unsigned(d.pins[p]));
+        c1 = wave_sum(c1);
+        if (l == 0) {
+            const unsigned c0 = unsigned(q1 - q0) - c1;
+            d.cnt[2 * f] = c0;
+            d.cnt[2 * f + 1] = c1;
+            if (c0 > 0u && c1 > 0u) {
+                cutw += u64(d.cw[f]);
+                ++cut;
+            }
+        }
+    }
+    cutw = wave_sum(cutw);
+    cut = wave_sum(cut);
+    if (l == 0) {
+        ws[t >> 6] = cutw;
+        wn[t >> 6] = cut;
+    }
+    __syncthreads();
+    if (t == 0) {
+        const u64 allw = ws[0] + ws[1] + ws[2] + ws[3];
+        const unsigned all = wn[0] + wn[1] + wn[2] + wn[3];
+        if (all) {
+            atomicAdd(reinterpret_cast<u64*>(d.state + 3), allw);
+            atomicAdd(reinterpret_cast<u64*>(d.state + 4), u64(all));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// g(v) = sum of c(e) over {e on v : cnt(e, a) = 1} - sum of c(e) over {e on v :
+// cnt(e, 1 - a) = 0}, a = v's side.  Each sum is at most 2^31 - 1 (checked on
+// the host), so 32-bit arithmetic holds them.
+__global__ __launch_bounds__(256) void k_fmw_gains(FmwDev d) {
+    const int t = threadIdx.x, l = t & 63;
+    const long long v = blockIdx.x * 256ll + t;
+    int64_t i0 = 0, i1 = 0;
+    unsigned a = 0u;
+    if (v < d.n) {
+        i0 = d.inc_ptr[v];
+        i1 = d.inc_ptr[v + 1];
+        a = bit_of(d.side, unsigned(v));
+    }
+    const bool is_long = i1 - i0 > FG_LONG;
+    if (v < d.n && !is_long) {
+        int g = 0;
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t e = d.inc[i];
+            const int c = d.cw[e];
+            g += (ld(d.cnt + 2 * e + a) == 1u ? c : 0) - (ld(d.cnt + 2 * e + (1u - a)) == 0u ? c : 0);
+        }
+        d.gain[v] = g;
+    }
+    u64 todo = __ballot(is_long);
+    while (todo) {
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1ull;
+        const int64_t j0 = __shfl(i0, src, 64), j1 = __shfl(i1, src, 64);
+        const unsigned b = __shfl(a, src, 64);
+        unsigned up = 0u, dn = 0u;
+        for (int64_t i = j0 + l; i < j1; i += 64) {
+            const int64_t e = d.inc[i];
+            const unsigned c = unsigned(d.cw[e]);
+            up += ld(d.cnt + 2 * e + b) == 1u ? c : 0u;
+            dn += ld(d.cnt + 2 * e + (1u - b)) == 0u ? c : 0u;
+        }
+        up = wave_sum(up);
+        dn = wave_sum(dn);
+        if (l == 0) d.gain[v - l + src] = int(up) - int(dn);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// One pass, one workgroup, one launch: k_fm_pass with four differences.
+//
+// Selection is the same chunk-key reduction (key ((g + 2^31) << 32 | ~id), 0
+// for none; LDSK: the keys, the dirty bitmap and the dirty list in LDS).  Then
+// (1) w(top) of the two top keys is loaded, one more dependent load a move,
+// and a side has a candidate iff S[1 - a] + w(top) <= L_max; of two, the
+// greater g, then the heavier side, then the smaller id.  (2) The sides'
+// weights, L_max and (3) the best prefix's (c, d) are 64-bit.  (4) The
+// critical-net updates add +-c(e) where the unweighted pass adds +-1: with F =
+// cnt(e, a) and T = cnt(e, b) read before v goes from a to b, T = 0: +c for
+// every other pin; T = 1: -c for the pin on b; then F = 1: -c for every other
+// pin; F = 2: +c for the other pin on a.  Locked pins are skipped.
+template <bool LDSK>
+__global__ __launch_bounds__(FM_THREADS) void k_fmw_pass(FmwDev d, int stall, long long mlog_at, long long* rec) {
+    constexpr int W = FM_THREADS / 64;
+    __shared__ u64 s_keys[LDSK ? 2 * FM_LDS_CHUNKS : 2];
+    __shared__ unsigned s_dirty[LDSK ? FM_LDS_CHUNKS / 32 : 1];
+    __shared__ int s_dlist[LDSK ? FM_LDS_CHUNKS : 1];
+    __shared__ u64 s_red[2 * W];
+    __shared__ int s_nd;
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    const int nck = d.nchunks;
+    u64* keys;
+    unsigned* dirty;
+    int* dlist;
+    if constexpr (LDSK) {
+        keys = s_keys;
+        dirty = s_dirty;
+        dlist = s_dlist;
+    } else {
+        keys = d.gkeys;
+        dirty = d.gdirty;
+        dlist = d.gdlist;
+    }
+    auto ldk = [&](const u64* p) -> u64 {
+        if constexpr (LDSK) return *p;
+        else return ld(p);
+    };
+    auto stk = [&](u64* p, u64 k) {
+        if constexpr (LDSK) *p = k;
+        else st(p, k);
+    };
+    auto mark = [&](int c) {
+        const unsigned bit = 1u << (c & 31);
+        if (atomicOr(&dirty[c >> 5], bit) & bit) return;
+        const int at = atomicAdd(&s_nd, 1);  // (a chunk is listed once between two rescans: at < nck)
+        if (at < nck) {
+            if constexpr (LDSK) dlist[at] = c;
+            else st(dlist + at, c);
+        }
+    };
+    auto rescan = [&](int c) {  // the calling wave
+        u64 k0 = 0ull, k1 = 0ull;
+        const long long base = (long long)c * FM_CHUNK;
+#pragma unroll
+        for (int j = 0; j < FM_CHUNK / 64; ++j) {
+            const long long v = base + j * 64 + l;
+            if (v < d.n && !bit_of(d.lock, unsigned(v))) {
+                const unsigned g = unsigned(ld(d.gain + v)) + 0x80000000u;
+                const u64 k = (u64(g) << 32) | u64(~unsigned(v));
+                if (bit_of(d.side, unsigned(v))) k1 = k > k1 ? k : k1;
+                else k0 = k > k0 ? k : k0;
+            }
+        }
+        k0 = wave_max(k0);
+        k1 = wave_max(k1);
+        if (l == 0) {
+            stk(keys + c, k0);
+            stk(keys + nck + c, k1);
+            atomicAnd(&dirty[c >> 5], ~(1u << (c & 31)));
+        }
+    };
+
+    // the pass's start: locks = the nodes of no net, nothing dirty, every key scanned
+    const long long nwords = ((long long)d.n + 31) / 32;
+    for (long long i = t; i < nwords; i += FM_THREADS) st(d.lock + i, d.lock0[i]);
+    for (int i = t; i < (nck + 31) / 32; i += FM_THREADS) {
+        if constexpr (LDSK) dirty[i] = 0u;
+        else st(dirty + i, 0u);
+    }
+    if (t == 0) s_nd = 0;
+    wg_barrier();
+    for (int c = w; c < nck; c += W) rescan(c);
+    wg_barrier();
+
+    long long cut = d.state[0], s0 = d.state[1], s1 = d.state[2];
+    auto dist = [](long long x, long long y) { return x > y ? x - y : y - x; };
+    long long c_best = cut, d_best = dist(s0, s1);
+    int t_best = 0, tt = 0;
+    bool bad = false;
+    while (tt < d.n) {  // (a node moves at most once a pass)
+        // the sides' best keys
+        u64 m0 = 0ull, m1 = 0ull;
+        for (int c = t; c < nck; c += FM_THREADS) {
+            const u64 x = ldk(keys + c), y = ldk(keys + nck + c);
+            m0 = x > m0 ? x : m0;
+            m1 = y > m1 ? y : m1;
+        }
+        m0 = wave_max(m0);
+        m1 = wave_max(m1);
+        if (l == 0) {
+            s_red[w] = m0;
+            s_red[W + w] = m1;
+        }
+        wg_barrier();
+        m0 = 0ull;
+        m1 = 0ull;
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+            m0 = s_red[q] > m0 ? s_red[q] : m0;
+            m1 = s_red[W + q] > m1 ? s_red[W + q] : m1;
+        }
+        // the top nodes' weights and the choice (the same in every thread); a key that names no node is
+        // caught before its weight is read
+        const unsigned v0 = ~unsigned(m0), v1 = ~unsigned(m1);
+        if ((m0 != 0ull && v0 >= unsigned(d.n)) || (m1 != 0ull && v1 >= unsigned(d.n))) {
+            bad = true;
+            break;
+        }
+        const long long w0 = m0 != 0ull ? d.w[v0] : 0, w1 = m1 != 0ull ? d.w[v1] : 0;
+        const bool have0 = m0 != 0ull && s1 + w0 <= d.lmax, have1 = m1 != 0ull && s0 + w1 <= d.lmax;
+        if (!have0 && !have1) break;
+        const int g0 = int(unsigned(m0 >> 32) - 0x80000000u), g1 = int(unsigned(m1 >> 32) - 0x80000000u);
+        unsigned a;  // the side the node leaves
+        if (have0 && have1) a = g0 != g1 ? unsigned(g1 > g0) : s0 != s1 ? unsigned(s1 > s0) : unsigned(v1 < v0);
+        else a = have1 ? 1u : 0u;
+        const unsigned v = a ? v1 : v0;
+        const int g = a ? g1 : g0;
+        const long long wv = a ? w1 : w0;
+        // the move
+        cut -= g;
+        s0 += a ? wv : -wv;
+        s1 += a ? -wv : wv;
+        ++tt;
+        if (t == 0) {
+            atomicXor(d.side + (v >> 5), 1u << (v & 31u));
+            atomicOr(d.lock + (v >> 5), 1u << (v & 31u));
+            d.pass_nodes[tt - 1] = int32_t(v);
+            const long long at = mlog_at + tt - 1;
+            if (d.mlog && at < d.mlog_cap) d.mlog[at] = ek_fm_move{int32_t(v), g, cut};
+            mark(int(v / FM_CHUNK));
+        }
+        const long long dd = dist(s0, s1);
+        if (cut < c_best || (cut == c_best && dd < d_best)) {
+            c_best = cut;
+            d_best = dd;
+            t_best = tt;
+        }
+        // the gains of the free pins of v's nets, and the counts
+        const int64_t i0 = d.inc_ptr[v], i1 = d.inc_ptr[v + 1];
+        for (int64_t i = i0 + w; i < i1; i += W) {
+            const int64_t e = d.inc[i];
+            unsigned F = 0u, T = 0u;
+            if (l == 0) {
+                F = ld(d.cnt + 2 * e + a);
+                T = ld(d.cnt + 2 * e + (1u - a));
+                st(d.cnt + 2 * e + a, F - 1u);
+                st(d.cnt + 2 * e + (1u - a), T + 1u);
+            }
+            F = __shfl(F, 0, 64);
+            T = __shfl(T, 0, 64);
+            const bool all_up = T == 0u, one_to = T == 1u, all_dn = F == 1u, one_from = F == 2u;
+            if (!(all_up || one_to || all_dn || one_from)) continue;
+            const int c = d.cw[e];
+            const int64_t p1 = d.net_ptr[e + 1];
+            for (int64_t p = d.net_ptr[e] + l; p < p1; p += 64) {
+                const unsigned u = unsigned(d.pins[p]);
+                if (u == v || bit_of(d.lock, u)) continue;
+                const unsigned su = bit_of(d.side, u);
+                int dl = 0;
+                if (all_up) dl += c;
+                else if (one_to && su != a) dl -= c;
+                if (all_dn) dl -= c;
+                else if (one_from && su == a) dl += c;
+                if (dl) {
+                    atomicAdd(d.gain + u, dl);
+                    mark(int(u / FM_CHUNK));
+                }
+            }
+        }
+        if (stall > 0 && tt - t_best >= stall) break;
+        wg_barrier();
+        const int nd = min(s_nd, nck);
+        for (int j = w; j < nd; j += W) {
+            int c;
+            if constexpr (LDSK) c = dlist[j];
+            else c = ld(dlist + j);
+            if (c >= 0 && c < nck) rescan(c);
+        }
+        wg_barrier();
+        if (t == 0) s_nd = 0;
+    }
+    if (t == 0) {
+        rec[0] = bad ? -1 : tt;
+        rec[1] = t_best;
+        rec[2] = c_best;
+        rec[3] = d_best;
+        if (!bad) {  // (the weights as after the last move: k_fmw_rollback takes the undone moves' back)
+            d.state[0] = c_best;
+            d.state[1] = s0;
+            d.state[2] = s1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// A wave per undone move: the node's side bit flipped back, its nets' counts
+// and the sides' weights (state[1], state[2]) with it.  The entries are
+// distinct nodes, so each bit flips once; the counts and the weights change by
+// integer adds.
+__global__ __launch_bounds__(256) void k_fmw_rollback(FmwDev d, int first, int count) {
+    const int l = threadIdx.x & 63;
+    const long long j = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (j >= count) return;
+    const int32_t vs = d.pass_nodes[first + j];
+    if (vs < 0 || vs >= d.n) return;
+    const unsigned v = unsigned(vs);
+    unsigned b = l == 0 ? bit_of(d.side, v) : 0u;  // where it is now
+    b = __shfl(b, 0, 64);
+    const int64_t i1 = d.inc_ptr[v + 1];
+    for (int64_t i = d.inc_ptr[v] + l; i < i1; i += 64) {
+        const int64_t e = d.inc[i];
+        atomicAdd(d.cnt + 2 * e + b, 0xFFFFFFFFu);
+        atomicAdd(d.cnt + 2 * e + (1u - b), 1u);
+    }
+    if (l == 0) {
+        const u64 wv = u64(d.w[v]);
+        if (wv) {
+            atomicAdd(reinterpret_cast<u64*>(d.state + 1 + b), 0ull - wv);
+            atomicAdd(reinterpret_cast<u64*>(d.state + 2 - b), wv);
+        }
+        atomicXor(d.side + (v >> 5), 1u << (v & 31u));
+    }
+}
+
+// ---------------------------------------------------------------------------
+void fmw_counts(hipStream_t s, const FmwDev& d) {
+    const unsigned nb = unsigned((int64_t(d.nets) + FC_THREADS - 1) / FC_THREADS);
+    hipLaunchKernelGGL(k_fmw_counts, dim3(nb), dim3(FC_THREADS), 0, s, d);
+}
+
+void fmw_gains(hipStream_t s, const FmwDev& d) {
+    const unsigned nb = unsigned((int64_t(d.n) + 255) / 256);
+    hipLaunchKernelGGL(k_fmw_gains, dim3(nb), dim3(256), 0, s, d);
+}
+
+void fmw_pass(hipStream_t s, const FmwDev& d, int stall, long long mlog_at, long long* rec) {
+    if (d.nchunks <= FM_LDS_CHUNKS) hipLaunchKernelGGL(k_fmw_pass<true>, dim3(1), dim3(FM_THREADS), 0, s, d, stall, mlog_at, rec);
+    else hipLaunchKernelGGL(k_fmw_pass<false>, dim3(1), dim3(FM_THREADS), 0, s, d, stall, mlog_at, rec);
+}
+
+void fmw_rollback(hipStream_t s, const FmwDev& d, int first, int count) {
+    if (count <= 0) return;
+    const unsigned nb = unsigned((int64_t(count) + 3) / 4);
+    hipLaunchKernelGGL(k_fmw_rollback, dim3(nb), dim3(256), 0, s, d, first, count);
+}
+
+}  // namespace dev
+}  // namespace ek

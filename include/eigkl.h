@@ -75,6 +75,42 @@ int ek_hgr_dims(const ek_hgr* h, int64_t* nets, int64_t* nodes, int64_t* pins);
 int ek_hgr_copy_pins(const ek_hgr* h, int64_t* net_ptr /* nets+1 */, int32_t* pins /* pins */);
 void ek_hgr_free(ek_hgr* h);
 
+/* Optional weights.  A hypergraph may carry a node weight w(v) >= 0 per node
+ * and a net weight c(e) >= 1 per net (int32); an absent array stands for all
+ * ones.  Only the weighted FM refinement and ek_bipart_metrics_host read them:
+ * the Laplacian, the KL graph, the Lanczos solve, the splits, KL, the k-way
+ * paths and ek_fm_refine work on the structure alone.  ek_hgr_write writes a
+ * weighted hypergraph in the hMETIS form below (fmt, the net weights, the node
+ * weight lines) and an unweighted one as before; ek_hgr_induce and
+ * ek_hgr_largest_component carry the kept nodes' and the surviving nets'
+ * weights over.  No reference counterpart. */
+/* Copies node_w (nodes values) and net_w (nets values) into h; a NULL pointer
+ * clears that array.  EK_EINVAL for a node weight < 0 or a net weight < 1 (h
+ * is then unchanged). */
+int ek_hgr_set_weights(ek_hgr* h, const int32_t* node_w, const int32_t* net_w);
+/* 1 / 0 per array h carries.  Either pointer may be NULL. */
+int ek_hgr_weights(const ek_hgr* h, int32_t* has_node_w, int32_t* has_net_w);
+/* The weights, 1s for an absent array.  Either pointer may be NULL. */
+int ek_hgr_copy_weights(const ek_hgr* h, int32_t* node_w_out /* nodes */, int32_t* net_w_out /* nets */);
+/* The hMETIS reading of a .hgr file.  Lines beginning with '%' are comments
+ * anywhere.  Header "nets nodes [fmt]", fmt absent, 0, 1, 10 or 11.  Then
+ * `nets` net lines of 1-based pins, each beginning with the net's weight when
+ * fmt is 1 or 11; then, when fmt is 10 or 11, `nodes` lines of one node weight
+ * each.  Without net weights a blank or missing net line is an empty net, as
+ * in ek_hgr_read.  EK_EINVAL for any other fmt, a token that is no unsigned
+ * integer (a negative weight among them), a missing or zero net weight, a pin
+ * outside [1, nodes], a weight above INT32_MAX, a blank node weight line or
+ * too few of them.  ek_hgr_read is not this reader: it keeps the reference's
+ * line semantics and ignores a third header token. */
+int ek_hgr_read_weighted(const char* path, ek_hgr** out);
+/* out[0] = the weighted cut, the sum of c(e) over the cut nets; out[1] = the
+ * cut nets; out[2], out[3] = W_0, W_1, the node weight on side 0 and side 1.
+ * The conventions are the FM rule's: only nets with at least 2 distinct pins
+ * count, a repeated pin once.  side: one byte in {0, 1} per node (EK_EINVAL
+ * otherwise).  Written apart from the FM code: it is what the tests hold the
+ * weighted FM to. */
+int ek_bipart_metrics_host(const ek_hgr* h, const uint8_t* side /* nodes */, int64_t out[4]);
+
 /* ------------------------------------------------------------------ */
 /* Clique expansions (host, no GPU)                                     */
 /* ------------------------------------------------------------------ */
@@ -679,6 +715,58 @@ int ek_fm_refine_host(const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_ino
  * may follow. */
 int ek_fm_refine(ek_ctx* ctx, const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */,
                  int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, ek_fm_result* result);
+
+/* ------------------------------------------------------------------ */
+/* The weighted FM refinement: node weights under the balance bound, net */
+/* weights in the cut.  No reference counterpart.                        */
+/* ------------------------------------------------------------------ */
+/* The rule is the rule above with four replacements.  w(v) is
+ * the node weight and c(e) the net weight of h (1 where h carries no such
+ * array), W = sum of w(v), S_0 and S_1 the sides' weights; the cut is the sum
+ * of c(e) over the cut nets.
+ * (a) Gain: g(v) = sum of c(e) over {e on v : cnt(e, a) = 1} - sum of c(e)
+ * over {e on v : cnt(e, 1 - a) = 0}: moving v lowers the weighted cut by
+ * exactly g(v).  (b) Bound: L_max = floor((1 + imbalance) ceil(W / 2)).
+ * (c) Candidate: side a's top node is its unlocked node of deg > 0 of greatest
+ * g, ties to the smaller id; it is side a's candidate iff S[1 - a] + w(top) <=
+ * L_max.  Only the top node is tried: a top node that does not fit leaves its
+ * side without a candidate until the state changes, even when a lighter node
+ * of lower gain would fit (a choice of the rule: selection stays a pure
+ * max-key reduction).  (d) Of two candidates the greater g moves; equal g:
+ * the one from the heavier side (greater S_a); equal weights: the smaller id.
+ * d_t = |S_0 - S_1|.  Everything else (the best prefix over (c_t, d_t), stall,
+ * the rollback, counted passes, termination) is the unweighted rule word for
+ * word, and with every weight 1 this is that rule exactly.
+ * Ranges, each EK_EINVAL: the sum of c(e) over the participating nets on any
+ * one node is at most 2^31 - 1 (gains are int32); W and the sum of all c(e)
+ * are at most 2^62 (int64 with room to spare; int32 weights and counts cannot
+ * in fact exceed it); sides, imbalance and node count as for ek_fm_refine. */
+typedef struct {
+    int64_t n, total_weight, max_part; /* nodes; W; L_max */
+    int32_t passes, passes_run;        /* counted passes (t* > 0); passes run (at most one more) */
+    int64_t moves_tried, moves_kept;   /* sum of t and of t* over the passes run */
+    int64_t cut_before, cut;           /* the weighted cut of the sides given and of the sides returned */
+    int64_t cut_nets_before, cut_nets; /* the cut nets of the same */
+    int64_t w0, w1, n0, n1;            /* the sides' weights and node counts after the run */
+    double t_setup, t_passes, t_metrics; /* wall seconds (host clock) */
+} ek_fm_w_result;
+
+/* The weighted refinement on the host (no GPU): the checker of ek_fm_refine_w,
+ * single threaded and written from the rule, the gains of the pins of the
+ * moved node's nets recomputed from their definition after every move.
+ * Arguments as ek_fm_refine_host; ek_fm_opts and ek_fm_move are reused: a
+ * move's gain is the weighted g, its cut the weighted cut, and a pass_log row
+ * is moves tried, t*, the weighted cut and |S_0 - S_1| after the rollback. */
+int ek_fm_refine_w_host(const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */, int64_t* pass_log,
+                        int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, ek_fm_w_result* result);
+/* The same on the GPU: the same bytes in side_inout, pass_log and move_log and
+ * the same result integers.  Kernels of its own (kernels_fmw.hip) beside the
+ * unweighted ones; one record read per pass, the log and the sides once at
+ * the end.  EK_ESTATE on a multi-rank context.  Every buffer is local to the
+ * call and the context keeps nothing. */
+int ek_fm_refine_w(ek_ctx* ctx, const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */,
+                   int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap,
+                   ek_fm_w_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
