@@ -90,7 +90,7 @@ int sweep_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lan
 int fm_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
                     double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr, ek_fm_result* fr)
     __attribute__((weak));
-// fmw.cpp: the same on the hMETIS reading of the file, with ek_fm_refine_w, for `--fm EPS --weighted`
+// fm.cpp: the same on the hMETIS reading of the file, with ek_fm_refine_w, for `--fm EPS --weighted`
 int fmw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
                      double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr,
                      ek_fm_w_result* fr) __attribute__((weak));

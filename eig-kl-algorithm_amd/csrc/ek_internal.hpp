@@ -786,7 +786,9 @@ int sweep_select_blocks(int64_t window);
 void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, int64_t s_hi, int objective,
                   unsigned* part, const unsigned* span_part, int nspan, long long* rec);
 
-// kernels_fm.hip — the FM refinement of a bipartition (ek_fm_refine)
+// kernels_fm.hip — the FM refinement of a bipartition, unweighted (FmDev,
+// ek_fm_refine) and weighted (FmwDev, ek_fm_refine_w): one set of kernels,
+// instantiated for each struct
 constexpr int FM_CHUNK = 256;        // node ids per chunk key
 constexpr int FM_THREADS = 512;      // the pass's one workgroup
 constexpr int FM_LDS_CHUNKS = 2048;  // up to this many chunks the keys live in LDS, above it in global memory
@@ -806,53 +808,33 @@ struct FmDev {
     unsigned* gdirty;            // their dirty bitmap, (nchunks + 31) / 32 words, zero between launches
     int32_t* gdlist;             // the dirty chunks' list, nchunks
 };
-// cnt(e, .) of the side bitmap, and state[3] (zero before) += the cut nets.  nets > 0.
-void fm_counts(hipStream_t s, const FmDev& d);
-// gain[v] = g(v) of every node from the incidence and the counts
-void fm_gains(hipStream_t s, const FmDev& d);
-// one pass from state[0..2] (the cut and the sides' sizes) and gain[]: moves
-// until none is left or the stall test ends it, each written to pass_nodes
-// and, at mlog_at + t, to mlog.  rec[0..3] = moves tried, t*, c and d of the
-// best prefix; state[0..2] = the cut and sizes of that prefix.  The sides,
-// counts and locks are left as after the last move: fm_rollback undoes the
-// moves past t*.  rec[0] = -1: a key named no node (state unchanged).
-void fm_pass(hipStream_t s, const FmDev& d, int stall, long long mlog_at, long long* rec);
-// moves first .. first + count - 1 of pass_nodes flipped back, the counts with them
-void fm_rollback(hipStream_t s, const FmDev& d, int first, int count);
-
-// kernels_fmw.hip — the weighted FM refinement (ek_fm_refine_w): FmDev's
-// layout with the weights, 64-bit side weights and a 64-bit L_max.  The chunk
-// size, the workgroup and the LDS threshold are the unweighted pass's.
-struct FmwDev {
-    int n, nets, nchunks;
-    long long lmax;
-    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
-    const int32_t *pins, *inc;
-    const int32_t *cw, *w;       // c(e) per net, w(v) per node
-    unsigned *side, *lock;       // bitmaps, (n + 31) / 32 words; lock also holds the nodes of no net
-    const unsigned* lock0;       // the lock bitmap a pass starts from: the nodes of no net
-    int32_t* gain;               // n
-    unsigned* cnt;               // 2 a net: cnt(e, 0), cnt(e, 1)
-    long long* state;            // weighted cut, S0, S1, and fmw_counts' weighted cut and cut nets (5 words)
-    int32_t* pass_nodes;         // the pass's moved nodes, in order (n)
-    ek_fm_move* mlog;            // the run's move log, mlog_cap entries (may be null)
-    long long mlog_cap;
-    unsigned long long* gkeys;   // 2 * nchunks chunk keys (nchunks > FM_LDS_CHUNKS only)
-    unsigned* gdirty;            // their dirty bitmap, (nchunks + 31) / 32 words, zero between launches
-    int32_t* gdlist;             // the dirty chunks' list, nchunks
+// The weighted rule's: state is the weighted cut, S0, S1, and fm_counts'
+// weighted cut and cut nets (5 words).
+struct FmwDev : FmDev {
+    const int32_t *cw, *w;  // c(e) per net, w(v) per node
+    long long lmax;         // the 64-bit L_max: hides FmDev's, so d.lmax is the bound of either rule
 };
-// cnt(e, .) of the side bitmap; state[3] += the weighted cut, state[4] += the cut nets (zero before).  nets > 0.
-void fmw_counts(hipStream_t s, const FmwDev& d);
-// gain[v] = the weighted g(v) of every node from the incidence, the counts and c(e)
-void fmw_gains(hipStream_t s, const FmwDev& d);
-// one pass from state[0..2] (the weighted cut and the sides' weights) and
-// gain[], as fm_pass.  rec[0..3] = moves tried, t*, c and d of the best
-// prefix; state[0] = c, state[1..2] = the sides' weights after the LAST move:
-// fmw_rollback undoes the moves past t*, the weights included.  rec[0] = -1: a
-// key named no node (state unchanged).
-void fmw_pass(hipStream_t s, const FmwDev& d, int stall, long long mlog_at, long long* rec);
-// moves first .. first + count - 1 of pass_nodes flipped back, the counts and state[1..2] with them
-void fmw_rollback(hipStream_t s, const FmwDev& d, int first, int count);
+// D is FmDev or FmwDev in all four.
+// cnt(e, .) of the side bitmap, and state[3] (zero before) += the cut nets;
+// weighted: state[3] += the weighted cut, state[4] += the cut nets.  nets > 0.
+template <class D>
+void fm_counts(hipStream_t s, const D& d);
+// gain[v] = g(v) of every node from the incidence, the counts and, weighted, c(e)
+template <class D>
+void fm_gains(hipStream_t s, const D& d);
+// one pass from state[0..2] (the cut and the sides' sizes or weights) and
+// gain[]: moves until none is left or the stall test ends it, each written to
+// pass_nodes and, at mlog_at + t, to mlog.  rec[0..3] = moves tried, t*, c and
+// d of the best prefix; state[0] = c.  The sides, counts and locks are left as
+// after the last move: fm_rollback undoes the moves past t*.  state[1..2]:
+// unweighted, the sizes of the best prefix; weighted, the weights after the
+// LAST move, which fm_rollback takes back with the moves.  rec[0] = -1: a key
+// named no node (state unchanged).
+template <class D>
+void fm_pass(hipStream_t s, const D& d, int stall, long long mlog_at, long long* rec);
+// moves first .. first + count - 1 of pass_nodes flipped back, the counts (weighted: and state[1..2]) with them
+template <class D>
+void fm_rollback(hipStream_t s, const D& d, int first, int count);
 
 }  // namespace dev
 }  // namespace ek

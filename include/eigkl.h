@@ -760,10 +760,10 @@ typedef struct {
 int ek_fm_refine_w_host(const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */, int64_t* pass_log,
                         int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, ek_fm_w_result* result);
 /* The same on the GPU: the same bytes in side_inout, pass_log and move_log and
- * the same result integers.  Kernels of its own (kernels_fmw.hip) beside the
- * unweighted ones; one record read per pass, the log and the sides once at
- * the end.  EK_ESTATE on a multi-rank context.  Every buffer is local to the
- * call and the context keeps nothing. */
+ * the same result integers.  The weighted instantiation of the unweighted
+ * path's kernels (kernels_fm.hip); one record read per pass, the log and the
+ * sides once at the end.  EK_ESTATE on a multi-rank context.  Every buffer is
+ * local to the call and the context keeps nothing. */
 int ek_fm_refine_w(ek_ctx* ctx, const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side_inout /* nodes */,
                    int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap,
                    ek_fm_w_result* result);
