@@ -1,7 +1,12 @@
-// What the runtime files of libeigkl_hip.so share (ctx.cpp, ctx_kl.cpp,
-// ctx_kway.cpp; host code over the HIP runtime + RCCL): the error macros, the
-// owning device buffer, the pinned upload staging, struct ek_ctx and the
-// helpers every file uses.  Included by them only.
+// What the runtime files of libeigkl_hip.so share (host code over the HIP
+// runtime + RCCL): the error macros, the owning device buffer, the pinned
+// upload staging, struct ek_ctx and the helpers that cross the files.
+// Included by them only:
+//   ctx.cpp          the context's lifetime, streams, the Uploader
+//   ctx_comm.cpp     collectives and their timing, shard map, halo exchange
+//   ctx_spmv.cpp     SpMV set-up (host rows / device Laplacian build), ek_spmv*
+//   ctx_lanczos.cpp  the implicitly restarted Lanczos, ek_lanczos_fiedler
+//   ctx_kl.cpp, ctx_kway.cpp, ctx_sweep.cpp, ctx_fm.cpp   the partition drivers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -260,5 +265,21 @@ inline ek_ctx* check_ctx(ek_ctx* c) {
     set_device(c);
     return c;
 }
+
+// What crosses the runtime files (each is commented where it is defined);
+// hidden: internal to the library, not part of its dynamic symbols.
+#pragma GCC visibility push(hidden)
+// ctx_comm.cpp: the collectives seam, the shard map and the halo exchange
+void allreduce(ek_ctx* c, double* p, size_t count);
+void allgather(ek_ctx* c, const double* send, size_t count, double* recv, hipStream_t st = nullptr);
+void comm_collect(ek_ctx* c);
+void set_shard(ek_ctx* c, int64_t n, const std::vector<int64_t>& off);
+int64_t x_extent(const ek_ctx* c);
+bool halo_build(ek_ctx* c, int32_t* col, int64_t nnz);
+void halo_exchange(ek_ctx* c, const double* src, hipStream_t st);
+// ctx_spmv.cpp: the matrix as the SpMV launches take it
+ek::dev::SpmvMat spmv_mat(const ek_ctx* c);
+ek::dev::SpmvMat own_mat(const ek_ctx* c);
+#pragma GCC visibility pop
 
 }  // namespace ek::rt

@@ -94,7 +94,7 @@ struct ek_hgr {
     std::vector<int32_t> node_w, net_w;
 };
 namespace ek {
-// ek_spmv_setup_pins for an ek_hgr (ctx.cpp): its pins need no range scan
+// ek_spmv_setup_pins for an ek_hgr (ctx_spmv.cpp): its pins need no range scan
 int spmv_setup_hgr(ek_ctx* c, const ek_hgr& h, int32_t* on_device);
 }  // namespace ek
 
@@ -225,7 +225,7 @@ typedef struct ihipEvent_t* hipEvent_t;
 // block sums the same partials in the same order — and block 0 publishes
 // fn2_out, alpha[step] = *a3 + h2[step], offd[step] = beta_step + h2[step-1]
 // with beta_step = *bov_i unless NaN, else sqrt(*fn2_i).  npart == null: none.
-constexpr int MAX_HALO_RANKS = 16;  // ranks of the halo exchange (ctx.cpp halo_build); more: the full all-gather
+constexpr int MAX_HALO_RANKS = 16;  // ranks of the halo exchange (ctx_comm.cpp halo_build); more: the full all-gather
 struct StepFin {
     const double* npart = nullptr;
     int nb = 0;
@@ -254,13 +254,13 @@ struct StepFin {
     // from ybase[row] (that SpMV's unscaled partial); own_lo == own_hi: none
     int own_lo = 0, own_hi = 0;
     const double* ybase = nullptr;
-    // the update inside the projection launch (ctx.cpp, PROI merged): the
+    // the update inside the projection launch (ctx_lanczos.cpp, PROI merged): the
     // fp32 shadow of the basis column (fl32(v), written with v) and the
     // projection's decision words + done counter, zeroed by block 0
     float* v32col = nullptr;
     unsigned* pub_rearm = nullptr;
     // the Lanczos mid-cycle check's copy, folded into the chunk's last SpMV
-    // (ctx.cpp chk_poll): block 0, once its finalize has published, copies
+    // (ctx_lanczos.cpp chk_poll): block 0, once its finalize has published, copies
     // alpha / offd [0, chk_b) and fn2 [0, chk_b) into the pinned slot chk_dst
     // (alpha at 0, offd at chk_m, fn2 at 2 chk_m), releases them to the
     // system and stores chk_seq to *chk_word, which the host polls
@@ -403,7 +403,7 @@ void remap_cols(hipStream_t s, long long nnz, int* col, const long long* off, in
 // a second call with the output arrays (orp: nr + 1) fills them
 long long own_split(hipStream_t s, long long nr, const int* rowptr, const int* col, const double* val, int lo, int hi,
                     int* cnt, long long* off, long long* tiles, int* orp, int* ocol, double* oval);
-// the halo exchange (ctx.cpp halo_build): sbuf[t] = f[sidx[t]] for t <
+// the halo exchange (ctx_comm.cpp halo_build): sbuf[t] = f[sidx[t]] for t <
 // nsend, the rank's own block X[base + k] = f[k] (k < nrows), and its
 // ||f||^2 partial P[0] = f[ldv]
 void halo_pack(hipStream_t s, const double* f, int ldv, const int* sidx, long long nsend, double* sbuf, double* X,
@@ -450,7 +450,7 @@ constexpr int GT_HANDOFF_UINTS = GT_NORM_CTR + 9 * 64;
 void gemvt(hipStream_t s, int ldv, int nrb, const double* V, int ncols, int has_u0, double u0val,
            int nreal, const double* w, double* part, int nrm = 0, unsigned* gctr = nullptr, double* h_out = nullptr,
            bool nt = false);
-// the sharded step (ctx.cpp factorize_mr): part for three vectors w, va, vb at
+// the sharded step (ctx_lanczos.cpp factorize_mr): part for three vectors w, va, vb at
 // once, part[(k*tot + j)*nrb + b], tot = ncols + has_u0, and ||w||^2 partials
 // at part[3*tot*nrb + b]
 void gemvt3(hipStream_t s, int ldv, int nrb, const double* V, int ncols, int has_u0, double u0val, int nreal,

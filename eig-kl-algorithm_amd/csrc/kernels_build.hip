@@ -496,7 +496,7 @@ void remap_cols(hipStream_t s, long long nnz, int* col, const long long* off, in
         hipLaunchKernelGGL(k_remap_cols, dim3(grid_of(nnz)), dim3(BT), 0, s, nnz, col, off, nranks, slot);
 }
 
-// The owned-slot part of a sharded rank's rows (ctx.cpp factorize_mr: its
+// The owned-slot part of a sharded rank's rows (ctx_lanczos.cpp factorize_mr: its
 // SpMV runs while the all-gather of the other slots is in flight): per local
 // row the entries whose slot-layout column lies in [lo, hi) — a contiguous
 // run, the columns are sorted — counted, then copied with LOCAL column ids
@@ -541,7 +541,7 @@ long long own_split(hipStream_t s, long long nr, const int* rowptr, const int* c
     return tot;
 }
 
-// The halo exchange of the sharded step (ctx.cpp halo_build): one launch
+// The halo exchange of the sharded step (ctx_comm.cpp halo_build): one launch
 // packs every peer's message and this rank's own block of the compact x.
 // Messages: sbuf[t] = f[sidx[t]] for t < nsend (sidx = the rows each peer
 // reads, each message closed by the index ldv: this rank's ||f||^2

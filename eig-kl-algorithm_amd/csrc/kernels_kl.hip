@@ -2600,7 +2600,7 @@ void net_cut(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t*
 // on the host (io.cpp, solve.cpp), without the vector's round trip.
 
 // out = x * sgn: the normalised, sign-fixed Ritz vector, the same IEEE
-// products as the host's v_out[i] = v[i] * sgn (ctx.cpp)
+// products as the host's v_out[i] = v[i] * sgn (ctx_lanczos.cpp)
 __global__ __launch_bounds__(256) void k_fiedler_scale(const double* __restrict__ x, double sgn, int n,
                                                        double* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;

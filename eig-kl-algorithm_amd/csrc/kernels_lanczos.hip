@@ -403,7 +403,7 @@ __device__ __forceinline__ void gemvt_skip_tail(int ncols, int has_u0, int nrb, 
 // an abort word: the first waiter that gives up counts itself there, and
 // every other waiter of the launch sees it within 256 polls and gives up too,
 // so a broken hand-off costs one bound, not one per workgroup; the host then
-// fails the solve with EK_EHIP (ctx.cpp).
+// fails the solve with EK_EHIP (ctx_lanczos.cpp).
 __device__ __forceinline__ bool pro_aborted(int* err) {
     return __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
 }
@@ -871,7 +871,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 #undef EK_GEMVT_PARAMS
 #undef EK_GEMVT_ARGS
 
-// The sharded step's projection (ctx.cpp Lanczos::factorize_mr): the partial
+// The sharded step's projection (ctx_lanczos.cpp Lanczos::factorize_mr): the partial
 // dot products of THREE vectors with the same basis columns in one sweep of
 // V — w = L v_i, v_i and v_{i-1} — so the three-term coefficient alpha and the
 // Gram-Schmidt coefficients of f' = w - alpha v_i - beta v_{i-1} come out of
@@ -1875,7 +1875,7 @@ void three_term(hipStream_t s, int ldv, const double* apart, int nparts, double*
                        bov_i, fp, v32col);
 }
 
-// The breakdown restart vector (ctx.cpp inject): element g of the global
+// The breakdown restart vector (ctx_lanczos.cpp inject): element g of the global
 // sequence st_{g} = st0 * 48271^(g+1) mod (2^31 - 1), as double(st) / p - 0.5
 // — the host loop's values, each lane jumping ahead by square-and-multiply
 // (operands < 2^31, so every product fits 64 bits).  Padding rows get 0.

@@ -1,5 +1,5 @@
 """The N>1 data path on CPU (gloo, world_size 2): the row-sharded Lanczos
-exchange the HIP path runs over RCCL (ctx.cpp
+exchange the HIP path runs over RCCL (ctx_lanczos.cpp
 Lanczos::factorize_mr), restated in numpy on each rank with the product's host
 pieces (generator, Laplacian rows, the nnz-balanced shard map):
 
@@ -114,7 +114,7 @@ def _worker(rank, port, out):
             fn2 = sum(x[r * S + ldv] for r in range(WORLD))  # rank order: same bits on every rank
             b_prev = np.sqrt(fn2)
             v = f / b_prev
-            # the overlapped SpMV (ctx.cpp factorize_mr): the owned slot's
+            # the overlapped SpMV (ctx_lanczos.cpp factorize_mr): the owned slot's
             # entries summed from f itself (while the all-gather is in flight),
             # the halo's from the gathered x, the row sum starting from the
             # owned part, then scaled by 1/||f||
@@ -184,7 +184,7 @@ def test_shard_map_is_what_the_library_enforces():
 
 
 def _halo_worker(rank, world, port, out):
-    """ctx.cpp halo_build / halo_exchange restated: the request lists from the
+    """ctx_comm.cpp halo_build / halo_exchange restated: the request lists from the
     slot-layout columns, one all-gather of the counts and one of the lists
     (setup), then per step ONE exchange of packed messages (here the
     host-staged form: an all-gather of every rank's padded messages, of which

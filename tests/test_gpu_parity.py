@@ -533,7 +533,7 @@ def test_lanczos_pro_inlaunch_graph_replays(ek, tmp_path, which):
 
 @pytest.mark.parametrize("name", ["ibm01", "industry2", "fract"])
 def test_lanczos_multirank_step_sequence_on_one_gpu(ek, tmp_path, name):
-    """The step sequence the sharded path runs (ctx.cpp factorize_mr: the
+    """The step sequence the sharded path runs (ctx_lanczos.cpp factorize_mr: the
     rank's ||f||^2 through the all-gather slot, one sweep projecting w, v_i and
     v_{i-1}, alpha and the projection of f' from one all-reduce; the
     collectives are no-ops at one rank) against the fused single-GPU step:

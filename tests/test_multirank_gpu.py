@@ -317,7 +317,7 @@ def test_two_rank_sharded_lanczos_syn10_config4():
 def test_rccl_one_rank_production_path(ek, monkeypatch, name, reorth):
     """The RCCL production path on the 1-GPU pool: under
     EK_COMM_FORCE a 1-rank context creates a real RCCL communicator
-    (ncclCommInitRank, nranks 1) and runs the sharded step (ctx.cpp
+    (ncclCommInitRank, nranks 1) and runs the sharded step (ctx_lanczos.cpp
     factorize_mr: the slot layout with the ||f||^2 tail, ncclAllGather of the
     slots, ONE in-place ncclAllReduce of the projections, stream order).  The
     Fiedler pair must meet the pre_saved_EIG tolerances, the same forced path
@@ -398,7 +398,7 @@ def test_rccl_one_rank_production_path(ek, monkeypatch, name, reorth):
 def test_sharded_step_reprojection(ek, monkeypatch, name):
     """the sharded step projects f' by linearity, exact to
     eps ||w|| rather than eps ||f'||; where f' cancels (||f'||^2 <
-    2^-20 ||w||^2) the driver projects the next vector once more (ctx.cpp
+    2^-20 ||w||^2) the driver projects the next vector once more (ctx_lanczos.cpp
     Lanczos::repair).  The bar is raised (EK_MR_CANCEL=0.4) so the repair runs
     on many steps: the run must still meet the golden's tolerances with the
     basis orthonormal to 1e-12 at every restart (EK_LANCZOS_ORTHO), on the

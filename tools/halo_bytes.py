@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Bytes a rank receives per sharded Lanczos step: the all-gather of whole
-slots (ctx.cpp exchange_f) against the halo exchange (halo_build: only the
+slots (ctx_lanczos.cpp exchange_f) against the halo exchange (halo_build: only the
 rows of other ranks its columns read, + one ||f||^2 partial per peer), from
 the nnz-balanced shard map and the Laplacian rows (host only, no GPU).
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU model of the product's implicitly restarted Lanczos (ctx.cpp
+"""CPU model of the product's implicitly restarted Lanczos (ctx_lanczos.cpp
 ek_lanczos_fiedler: deflated u0, ncv 100, nev 1, restart floor ncv/5,
 convergence checked every chunk) with FULL classical Gram-Schmidt per step
 against PARTIAL reorthogonalisation (Simon's omega recurrence, as in
