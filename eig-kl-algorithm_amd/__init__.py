@@ -130,6 +130,13 @@ class SweepResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _SWEEP_TIMES])
 
 
+class SweepWResult(_AbiStruct):
+    """eigkl.h ek_sweep_w_result (the weighted sweep cut)."""
+    _fields_ = ([(k, _I64) for k in ("n", "n0", "n1", "s_lo", "s_hi", "feasible", "total_weight", "max_part", "w0", "w1",
+                                     "cut", "cut_nets", "cut_half", "spanning_nets")]
+                + [(k, ctypes.c_double) for k in _SWEEP_TIMES])
+
+
 FM_CHUNK = 256  # ek_internal.hpp FM_CHUNK: node ids per chunk key of the FM pass
 FM_LDS_CHUNKS = 2048  # ek_internal.hpp FM_LDS_CHUNKS: above this many chunks the keys live in global memory
 FM_THREADS = 512  # ek_internal.hpp FM_THREADS: the FM pass's one workgroup
@@ -266,6 +273,10 @@ _sig("ek_sweep_cut_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _
 _sig("ek_sweep_cut", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
 _sig("ek_kl_set_partition_fiedler_sweep", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts),
      ctypes.POINTER(SweepResult))
+_sig("ek_sweep_cut_w_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, _P, ctypes.POINTER(SweepWResult))
+_sig("ek_sweep_cut_w", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, _P, ctypes.POINTER(SweepWResult))
+_sig("ek_kl_set_partition_fiedler_sweep_w", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts),
+     ctypes.POINTER(SweepWResult))
 _sig("ek_fm_default_opts", None, ctypes.POINTER(FmOpts))
 _sig("ek_fm_refine_host", ctypes.c_int, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64, ctypes.POINTER(FmResult))
 _sig("ek_fm_refine", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64, ctypes.POINTER(FmResult))
@@ -366,8 +377,8 @@ class Hypergraph:
 
     def set_weights(self, node_w=None, net_w=None):
         """Node weights (>= 0, one per node) and net weights (>= 1, one per net); None clears that array, which
-        then stands for all ones (ek_hgr_set_weights).  Only the weighted FM refinement and bipart_metrics_host
-        read them."""
+        then stands for all ones (ek_hgr_set_weights).  Only the weighted FM refinement, the weighted sweep cut
+        and bipart_metrics_host read them."""
         nets, nodes, _ = self.dims()
         node_w = None if node_w is None else np.ascontiguousarray(node_w, np.int32)
         net_w = None if net_w is None else np.ascontiguousarray(net_w, np.int32)
@@ -578,6 +589,32 @@ def sweep_cut_host(hgr, v, imbalance=0.03, ratio=False):
     host (ek_sweep_cut_host, the device path's checker): the minimum cut, or with ratio the ratio cut.
     Returns (result dict, order, profile): order[r] the node at rank r, profile[s] the nets cut by split s."""
     return _sweep_cut(lambda *a: _lib.ek_sweep_cut_host(hgr._h, *a), "sweep_cut_host", hgr, v, imbalance, ratio)
+
+
+def _sweep_w_result(r):
+    return {name: getattr(r, name) for name, _ in SweepWResult._fields_}
+
+
+def _sweep_cut_w(call, what, hgr, v, imbalance):
+    v = np.ascontiguousarray(v, np.float64)
+    if len(v) != hgr.nodes:
+        raise ValueError(f"v has {len(v)} entries for {hgr.nodes} nodes")
+    o = _sweep_opts(imbalance, False)
+    order = np.full(len(v), -1, np.int32)
+    profile = np.full(len(v) + 1, -1, np.int64)
+    prefix = np.full(len(v) + 1, -1, np.int64)
+    r = SweepWResult()
+    _chk(call(_p(v), ctypes.byref(o), _p(order), _p(profile), _p(prefix), ctypes.byref(r)), what)
+    return _sweep_w_result(r), order, profile, prefix
+
+
+def sweep_cut_w_host(hgr, v, imbalance=0.03):
+    """The weighted sweep cut of v over hgr's nets and weights, on the host (ek_sweep_cut_w_host, the device
+    path's checker): the least weighted cut among the splits whose two sides weigh at most L_max = floor((1 +
+    imbalance) ceil(W / 2)), or, when there is none (feasible = 0), the split closest to balance.
+    Returns (result dict, order, profile_w, prefix): order[r] the node at rank r, profile_w[s] the weight of the
+    nets cut by split s, prefix[s] the weight of side 1 of split s (int64 both)."""
+    return _sweep_cut_w(lambda *a: _lib.ek_sweep_cut_w_host(hgr._h, *a), "sweep_cut_w_host", hgr, v, imbalance)
 
 
 def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap, result_type=None):
@@ -884,6 +921,21 @@ class Context:
              "kl_set_partition_fiedler_sweep")
         self._n01 = (r.n0, r.n1)
         return _sweep_result(r)
+
+    def sweep_cut_w(self, hgr, v, imbalance=0.03):
+        """sweep_cut_w_host on the GPU, on an uploaded copy of v (ek_sweep_cut_w): the same order, profile_w,
+        prefix and result integers.  Returns (result dict, order, profile_w, prefix)."""
+        return _sweep_cut_w(lambda *a: _lib.ek_sweep_cut_w(self._c, hgr._h, *a), "sweep_cut_w", hgr, v, imbalance)
+
+    def kl_set_partition_fiedler_sweep_w(self, hgr, imbalance=0.03):
+        """The weighted sweep cut of the Fiedler vector left on this context, then kl_set_partition_fiedler_rank
+        at its n1 (ek_kl_set_partition_fiedler_sweep_w).  Returns the result dict."""
+        o = _sweep_opts(imbalance, False)
+        r = SweepWResult()
+        _chk(_lib.ek_kl_set_partition_fiedler_sweep_w(self._c, hgr._h, ctypes.byref(o), ctypes.byref(r)),
+             "kl_set_partition_fiedler_sweep_w")
+        self._n01 = (r.n0, r.n1)
+        return _sweep_w_result(r)
 
     def rank_split_device(self, v, n1):
         """rank_split run by the device kernels on an uploaded copy of v (ek_rank_split_device)."""

@@ -54,6 +54,15 @@
 //                        node weights under the bound, net weights in the cut.
 //                        Lanczos, the split and KL ignore the weights.  The line
 //                        printed begins "fmw:" instead of "fm:"
+//   --sweep-weighted     with --sweep, --fm and --weighted, not with
+//                        --sweep-ratio: the weighted sweep cut
+//                        (ek_kl_set_partition_fiedler_sweep_w: net weights in the
+//                        profile, node weights in the window) instead of the count
+//                        sweep; the line printed begins "sweepw:" instead of
+//                        "sweep:"
+//   --no-kl              with --sweep-weighted: no KL graph and no KL loop (KL
+//                        swaps pairs and ignores weights, so it can leave the
+//                        bound); the sweep's sides go straight to ek_fm_refine_w
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -94,6 +103,12 @@ int fm_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int 
 int fmw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
                      double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr,
                      ek_fm_w_result* fr) __attribute__((weak));
+// sweepw.cpp: the weighted sweep split (no_kl: without the KL loop), then ek_fm_refine_w, for
+// `--sweep EPS --sweep-weighted --fm EPS --weighted [--no-kl]`
+// (stall < 0: the default)
+int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, double sweep_eps, int no_kl,
+                        double imbalance, int max_passes, int stall, ek_sweep_w_result* sr, ek_kl_result* kr,
+                        ek_fm_w_result* fr) __attribute__((weak));
 }
 
 namespace {
@@ -112,6 +127,7 @@ struct Opts {
     double fm_eps = 0.0;
     int fm_passes = 0, fm_stall = -1;  // (-1: the default)
     bool weighted = false;             // --weighted
+    bool sweep_weighted = false, no_kl = false;  // --sweep-weighted, --no-kl
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -347,6 +363,11 @@ constexpr const char* FMW_USAGE =
     "Usage: gKL2 <input_file> -EIG [--sweep <imbalance> [--sweep-ratio]] --fm <imbalance> --weighted [--fm-passes <P>] "
     "[--fm-stall <S>]  (--weighted needs --fm and excludes --k; the file is read as hMETIS reads it, fmt 0, 1, 10 or "
     "11; the FM refinement weighs nodes and nets, while Lanczos, the split and KL ignore the weights)\n";
+constexpr const char* SWEEPW_USAGE =
+    "Usage: gKL2 <input_file> -EIG --sweep <imbalance> --sweep-weighted --fm <imbalance> --weighted [--no-kl] "
+    "[--fm-passes <P>] [--fm-stall <S>]  (--sweep-weighted needs gKL2, -EIG, --sweep, --fm and --weighted, and excludes "
+    "--sweep-ratio and --k: the sweep cut weighs nets in its profile and nodes in its window; --no-kl needs "
+    "--sweep-weighted: the sweep's sides go to the weighted FM refinement without the KL loop)\n";
 
 // gKL2 <in.hgr> -EIG [--sweep EPS] --fm EPS: the usual output (or the sweep's line), one line beginning "fm:",
 // results/<base>.part.2
@@ -368,11 +389,26 @@ int run_fm(const Opts& o) {
                     (long long)kr.iterations, (long long)kr.best_iter);
     };
     if (o.weighted) {
-        if (!ek::fmw_file_for_cli) throw Fail{"this build carries no weighted FM refinement"};
         ek_fm_w_result wr{};
-        check(ek::fmw_file_for_cli(ci.get(), o.input.c_str(), &so, o.sweep ? 1 : 0, o.sweep_eps, o.sweep_ratio ? 1 : 0,
-                                   o.fm_eps, o.fm_passes, o.fm_stall, &sr, &kr, &wr), "weighted FM refinement");
-        print_sweep_and_kl();
+        if (o.sweep_weighted) {
+            if (!ek::sweepw_file_for_cli) throw Fail{"this build carries no weighted sweep cut"};
+            ek_sweep_w_result wsr{};
+            check(ek::sweepw_file_for_cli(ci.get(), o.input.c_str(), &so, o.sweep_eps, o.no_kl ? 1 : 0, o.fm_eps,
+                                          o.fm_passes, o.fm_stall, &wsr, &kr, &wr), "weighted sweep cut");
+            std::printf("sweepw: imbalance %g, window %lld..%lld (max_part %lld), feasible %lld, n1 %lld, w0 %lld | w1 %lld, "
+                        "total_weight %lld, cut_half %lld, cut %lld, cut_nets %lld\n", o.sweep_eps, (long long)wsr.s_lo,
+                        (long long)wsr.s_hi, (long long)wsr.max_part, (long long)wsr.feasible, (long long)wsr.n1,
+                        (long long)wsr.w0, (long long)wsr.w1, (long long)wsr.total_weight, (long long)wsr.cut_half,
+                        (long long)wsr.cut, (long long)wsr.cut_nets);
+            if (!o.no_kl)
+                std::printf("kl: net_cut_best %lld (%lld swaps, best prefix %lld)\n", (long long)kr.net_cut_best,
+                            (long long)kr.iterations, (long long)kr.best_iter);
+        } else {
+            if (!ek::fmw_file_for_cli) throw Fail{"this build carries no weighted FM refinement"};
+            check(ek::fmw_file_for_cli(ci.get(), o.input.c_str(), &so, o.sweep ? 1 : 0, o.sweep_eps, o.sweep_ratio ? 1 : 0,
+                                       o.fm_eps, o.fm_passes, o.fm_stall, &sr, &kr, &wr), "weighted FM refinement");
+            print_sweep_and_kl();
+        }
         std::printf("fmw: imbalance %g, cut_before %lld, cut %lld, cut_nets_before %lld, cut_nets %lld, passes %d, moves "
                     "kept %lld / tried %lld, w0 %lld, w1 %lld, total_weight %lld, max_part %lld, n0 %lld, n1 %lld, %.6f s "
                     "(fmw), %.3f s -> results/%s.part.2\n", o.fm_eps, (long long)wr.cut_before, (long long)wr.cut,
@@ -448,6 +484,8 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 if (o.fm_stall < 0) throw Fail{"--fm-stall takes a move count >= 0"};
             }
             else if (a == "--weighted") o.weighted = true;
+            else if (a == "--sweep-weighted") o.sweep_weighted = true;
+            else if (a == "--no-kl") o.no_kl = true;
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -467,6 +505,12 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         }
     }
     try {
+        if ((o.sweep_weighted || o.no_kl) &&
+            (!o.sweep_weighted || !o.sweep || !o.fm || !o.weighted || o.sweep_ratio || o.kway || o.tool != "gKL2" ||
+             !(pos.size() == 2 && pos[1] == "-EIG"))) {
+            std::printf("%s", SWEEPW_USAGE);
+            return 1;
+        }
         if ((o.sweep || o.sweep_ratio) && o.tool != "gKL2") {
             std::printf("Usage: gKL2 <input_file> -EIG --sweep <imbalance> [--sweep-ratio]  (--sweep needs gKL2)\n");
             return 1;

@@ -280,6 +280,15 @@ void halo_exchange(ek_ctx* c, const double* src, hipStream_t st);
 // ctx_spmv.cpp: the matrix as the SpMV launches take it
 ek::dev::SpmvMat spmv_mat(const ek_ctx* c);
 ek::dev::SpmvMat own_mat(const ek_ctx* c);
+// ctx_sweep.cpp: the sort of the sweep cuts (ek_sweep_cut, ek_sweep_cut_w):
+// order[r] the node at rank r of v (device, n doubles) and pos[order[r]] = r;
+// scan_tmp is left large enough for sweep_scan over n + 1 words
+struct SweepSort {
+    DBuf keys[2], ids[2], ghist, table, scan_tmp, pos;
+    int cur = 0;
+    const int32_t* order() const { return ids[cur].as<int32_t>(); }
+};
+void sweep_sort(ek_ctx* c, const double* v, int64_t n, SweepSort& out);
 #pragma GCC visibility pop
 
 }  // namespace ek::rt

@@ -4,29 +4,16 @@
 
 using namespace ek::rt;
 
-namespace {
-
-using clk = std::chrono::steady_clock;
-double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
-
-// The sweep cut of v (device, n doubles) over h's nets.  Every buffer is local
-// to the call.  Host synchronisations: one 8-KiB read of the passes' digit
-// counts (a pass whose digit all keys share is skipped), one after the
-// profile (for its time), one for the 32-byte result record; order and
-// profile are read only when asked for.
-void sweep_on_device(ek_ctx* c, const ek_hgr* h, const double* v, const ek_sweep_opts& o, int32_t* order_out,
-                     int32_t* profile_out, ek_sweep_result* result) {
+// The stable radix sort of the n keys (ord(v[i]), i) and its inverse, for both
+// sweep cuts.  One host synchronisation inside: the 8-KiB read of the passes'
+// digit counts (a pass whose digit all keys share is skipped); one at the end.
+void ek::rt::sweep_sort(ek_ctx* c, const double* v, int64_t n, SweepSort& out) {
     hipStream_t s = c->stream;
-    const int64_t n = h->nodes;
     const int ni = int(n);
-    ek_sweep_result r{};
-    ek::sweep_window(n, o.imbalance, r);
-
-    // sort
-    auto t = clk::now();
     const int nt = ek::dev::sweep_tiles(ni);
     const long long table_words = 256ll * nt;
-    DBuf keys[2], ids[2], ghist, table, scan_tmp, pos;
+    DBuf (&keys)[2] = out.keys, (&ids)[2] = out.ids;
+    DBuf &ghist = out.ghist, &table = out.table, &scan_tmp = out.scan_tmp, &pos = out.pos;
     for (int b = 0; b < 2; ++b) {
         keys[b].ensure(size_t(n) * 8);
         ids[b].ensure(size_t(n) * 4);
@@ -58,10 +45,36 @@ void sweep_on_device(ek_ctx* c, const ek_hgr* h, const double* v, const ek_sweep
         HIPCHK(hipGetLastError());
         cur ^= 1;
     }
-    const int32_t* order = ids[cur].as<int32_t>();
-    ek::dev::sweep_pos(s, order, ni, pos.as<int32_t>());
+    out.cur = cur;
+    ek::dev::sweep_pos(s, out.order(), ni, pos.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
+}
+
+namespace {
+
+using clk = std::chrono::steady_clock;
+double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
+
+// The sweep cut of v (device, n doubles) over h's nets.  Every buffer is local
+// to the call.  Host synchronisations: one 8-KiB read of the passes' digit
+// counts (a pass whose digit all keys share is skipped), one after the
+// profile (for its time), one for the 32-byte result record; order and
+// profile are read only when asked for.
+void sweep_on_device(ek_ctx* c, const ek_hgr* h, const double* v, const ek_sweep_opts& o, int32_t* order_out,
+                     int32_t* profile_out, ek_sweep_result* result) {
+    hipStream_t s = c->stream;
+    const int64_t n = h->nodes;
+    const int ni = int(n);
+    ek_sweep_result r{};
+    ek::sweep_window(n, o.imbalance, r);
+
+    // sort
+    auto t = clk::now();
+    SweepSort st;
+    sweep_sort(c, v, n, st);
+    const int32_t* order = st.order();
+    DBuf &scan_tmp = st.scan_tmp, &pos = st.pos;
     r.t_sort = since(t);
 
     // profile

@@ -193,6 +193,13 @@ void refine_prepare(const ek_hgr& h, RefineInput& in);
 ek_sweep_opts sweep_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts);
 void sweep_window(int64_t n, double imbalance, ek_sweep_result& r);
 
+// sweepw.cpp — what the host and the device weighted sweep cut share: the
+// argument checks (sweep_check's, objective 1 refused, every w(v) >= 0 and
+// c(e) >= 1, W and the sum of c(e) at most 2^62) and n, W, L_max =
+// refine_max_part(W, 2, imbalance) of the result
+ek_sweep_opts sweepw_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts,
+                           ek_sweep_w_result& r);
+
 // fm.cpp — what the host and the device FM refinement share besides
 // refine_max_part and refine_prepare: the argument checks (EK_EINVAL as
 // eigkl.h lists it; the opts with the defaults filled in)
@@ -785,6 +792,31 @@ void sweep_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int3
 int sweep_select_blocks(int64_t window);
 void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, int64_t s_hi, int objective,
                   unsigned* part, const unsigned* span_part, int nspan, long long* rec);
+
+// kernels_sweepw.hip — the weighted sweep cut (ek_sweep_cut_w): the sort, pos
+// and the count profile's scan are kernels_sweep.hip's
+constexpr int SWEEPW_SCAN_BLOCK = 2048;  // 64-bit words per workgroup of the scan
+constexpr int SWEEPW_SCAN_TOP = 256;     // block sums per step of the top scan's one workgroup
+constexpr int SWEEPW_REC = 10;           // words of the result record
+// diffw (n + 1 int64 words, zero before): +c(e) at lo + 1, -c(e) at hi + 1 of
+// every net with lo < hi (cw null: c = 1); diff (n + 1 words, zero before) and
+// span_part (sweep_span_blocks(nets) words) as sweep_spans
+void sweepw_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* cw,
+                  const int32_t* pos, int n, unsigned long long* diffw, unsigned* diff, unsigned* span_part);
+// pw[0] = 0, pw[r + 1] = w[order[r]] (w null: 1): its inclusive scan is P
+void sweepw_gather(hipStream_t s, const int32_t* order, const int32_t* w, int n, unsigned long long* pw);
+// inclusive prefix sum of data[0:count) in place, modulo 2^64; tmp:
+// sweepw_scan_tmp_words(count) words.  Any count below 2^31 (see the kernels).
+size_t sweepw_scan_tmp_words(long long count);
+void sweepw_scan(hipStream_t s, unsigned long long* data, long long count, unsigned long long* tmp);
+// the choice over s = 1 .. n - 1 from profile_w and P (n + 1 words each), W
+// and L_max; part: 5 * sweepw_select_blocks(n) words.  rec[0..9] = s* (-1:
+// none), feasible, s_lo, s_hi, profile_w[s*], profile[s*], profile_w[n / 2],
+// the sum of span_part[0:nspan), P[s*], P[n]
+int sweepw_select_blocks(int n);
+void sweepw_select(hipStream_t s, const unsigned long long* profw, const unsigned long long* prefix,
+                   const unsigned* profile, int n, unsigned long long total, unsigned long long max_part,
+                   unsigned long long* part, const unsigned* span_part, int nspan, long long* rec);
 
 // kernels_fm.hip — the FM refinement of a bipartition, unweighted (FmDev,
 // ek_fm_refine) and weighted (FmwDev, ek_fm_refine_w): one set of kernels,

@@ -77,9 +77,10 @@ void ek_hgr_free(ek_hgr* h);
 
 /* Optional weights.  A hypergraph may carry a node weight w(v) >= 0 per node
  * and a net weight c(e) >= 1 per net (int32); an absent array stands for all
- * ones.  Only the weighted FM refinement and ek_bipart_metrics_host read them:
- * the Laplacian, the KL graph, the Lanczos solve, the splits, KL, the k-way
- * paths and ek_fm_refine work on the structure alone.  ek_hgr_write writes a
+ * ones.  Only the weighted FM refinement, the weighted sweep cut
+ * (ek_sweep_cut_w*) and ek_bipart_metrics_host read them: the Laplacian, the
+ * KL graph, the Lanczos solve, the median, rank and count-sweep splits, KL, the
+ * k-way paths and ek_fm_refine work on the structure alone.  ek_hgr_write writes a
  * weighted hypergraph in the hMETIS form below (fmt, the net weights, the node
  * weight lines) and an unweighted one as before; ek_hgr_induce and
  * ek_hgr_largest_component carry the kept nodes' and the surviving nets'
@@ -645,6 +646,78 @@ int ek_sweep_cut(ek_ctx* ctx, const ek_hgr* h, const double* v_host, const ek_sw
  * result may be NULL.  No reference counterpart. */
 int ek_kl_set_partition_fiedler_sweep(ek_ctx* ctx, const ek_hgr* h, const ek_sweep_opts* opts,
                                       ek_sweep_result* result);
+
+/* ------------------------------------------------------------------ */
+/* The weighted sweep cut: net weights in the profile, node weights in  */
+/* the window.  No reference counterpart.                               */
+/* ------------------------------------------------------------------ */
+/* The rule is the rule above with these replacements.  w(v)
+ * is the node weight and c(e) the net weight of h (1 where h carries no such
+ * array), W = sum of w(v).  The order, order[r] and the meaning of split s are
+ * unchanged.
+ * (a) Profile: profile_w[s] = the sum of c(e) over {e : lo_e < s <= hi_e},
+ * int64, profile_w[0] = profile_w[n] = 0.  The count profile of the rule above
+ * is kept beside it, only to report the cut nets at the chosen split.
+ * (b) Prefix weight: P[s] = the sum of w(order[r]) over r < s, int64, P[0] = 0
+ * and P[n] = W.  Side 1 of split s weighs P[s], side 0 W - P[s].
+ * (c) Window: L_max = floor((1 + imbalance) ceil(W / 2)), the bound of
+ * ek_fm_refine_w.  Split s (1 <= s <= n - 1) is feasible iff P[s] <= L_max and
+ * W - P[s] <= L_max.  P is non-decreasing, so the feasible splits are one
+ * contiguous range s_lo..s_hi.  The range is certainly non-empty when max w(v)
+ * <= 2 L_max - W + 1: the feasible values of P are the integers of [W - L_max,
+ * L_max], 2 L_max - W + 1 >= 1 of them, and a walk from P[0] = 0 to P[n] = W
+ * whose steps are no longer than that count cannot jump over them: the first s
+ * with P[s] >= W - L_max has P[s] <= (W - L_max - 1) + (2 L_max - W + 1) =
+ * L_max; that s is neither 0 nor n unless L_max >= W, and then every split is
+ * feasible.  The range can be empty, for example when one node is heavier than
+ * L_max.
+ * (d) Choice.  Window not empty: feasible = 1 and s* is the window's least
+ * split under (profile_w[s], |2 P[s] - W|, s).  Window empty: feasible = 0,
+ * s_lo = s_hi = 0, and s* is the least split of 1..n-1 under (|2 P[s] - W|,
+ * profile_w[s], s), the closest the order comes to balance; this is not an
+ * error, as a start above L_max is none for ek_fm_refine_w.  Nodes of weight 0
+ * make P flat; the last key s keeps the order strict.
+ * (e) No ratio objective: its exact comparison would need products of three
+ * 62-bit numbers.  objective = 1 is EK_EINVAL in the weighted entries.
+ * Ranges, each EK_EINVAL: 2 <= n <= 2^31 - 2; W and the sum of all c(e) at
+ * most 2^62 (as for ek_fm_refine_w; int32 weights cannot in fact exceed it);
+ * imbalance finite and >= 0.
+ * With every weight 1, profile_w is the profile, P[s] = s, and the window and
+ * the choice are those of the rule above (objective 0). */
+typedef struct {
+    int64_t n, n0, n1;        /* nodes; side 0 and side 1 of the chosen split (n1 = s*) */
+    int64_t s_lo, s_hi;       /* the feasible splits (0, 0 when there is none) */
+    int64_t feasible;         /* 1: the window is not empty */
+    int64_t total_weight;     /* W */
+    int64_t max_part;         /* L_max */
+    int64_t w0, w1;           /* the sides' weights at s*: W - P[s*], P[s*] */
+    int64_t cut;              /* profile_w[s*] */
+    int64_t cut_nets;         /* the count profile at s* */
+    int64_t cut_half;         /* profile_w[floor(n / 2)] */
+    int64_t spanning_nets;    /* nets with lo < hi */
+    double t_sort, t_profile, t_select; /* wall seconds (host clock) */
+} ek_sweep_w_result;
+
+/* The weighted sweep cut on the host (no GPU): the checker of ek_sweep_cut_w,
+ * single threaded and written from the rule; it shares with the device path
+ * only the argument checks and L_max.  ek_sweep_opts is reused (objective must
+ * be 0).  order_out (n), profile_out (profile_w, n + 1 int64) and prefix_out
+ * (P, n + 1 int64) may be NULL.  EK_EINVAL as listed above. */
+int ek_sweep_cut_w_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opts, int32_t* order_out,
+                        int64_t* profile_out /* n + 1 */, int64_t* prefix_out /* n + 1 */, ek_sweep_w_result* result);
+/* The same on the GPU, on an uploaded copy of v_host: the same order, profile,
+ * prefix and result integers.  The host reads back the result record, and the
+ * three arrays only when asked for them.  Every buffer is local to the call
+ * and the context keeps nothing. */
+int ek_sweep_cut_w(ek_ctx* ctx, const ek_hgr* h, const double* v_host, const ek_sweep_opts* opts, int32_t* order_out,
+                   int64_t* profile_out /* n + 1 */, int64_t* prefix_out /* n + 1 */, ek_sweep_w_result* result);
+/* The weighted sweep cut of the Fiedler vector the last ek_lanczos_fiedler left
+ * on the device, then ek_kl_set_partition_fiedler_rank(ctx, result.n1): the
+ * context is in exactly the state that call leaves.  EK_ESTATE and EK_EINVAL
+ * as for ek_kl_set_partition_fiedler_sweep (and objective 1: EK_EINVAL).
+ * result may be NULL. */
+int ek_kl_set_partition_fiedler_sweep_w(ek_ctx* ctx, const ek_hgr* h, const ek_sweep_opts* opts,
+                                        ek_sweep_w_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Fiduccia-Mattheyses refinement of a bipartition on the integer net    */
