@@ -165,6 +165,37 @@ class FmWResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _FM_TIMES])
 
 
+MATCH_THREADS = 256  # ek_internal.hpp MATCH_THREADS: a workgroup of the matching's node kernels
+MATCH_SHORT = 32  # ek_internal.hpp MATCH_SHORT: above this many entries a node is taken by its whole wave
+ML_LEVELS = 32  # eigkl.h EK_ML_LEVELS
+
+
+class MatchOpts(_AbiStruct):
+    _fields_ = [("max_net", _I32), ("max_rounds", _I32), ("max_cluster", _I64)]
+
+
+class MatchResult(_AbiStruct):
+    _fields_ = [("n", _I64), ("n_coarse", _I64), ("pairs", _I64), ("rounds", _I32), ("pad", _I32),
+                ("eligible_nets", _I64), ("t_setup", ctypes.c_double), ("t_rounds", ctypes.c_double)]
+
+
+class MlOpts(_AbiStruct):
+    _fields_ = [("imbalance", ctypes.c_double), ("coarse_nodes", _I32), ("max_levels", _I32), ("match", MatchOpts),
+                ("fm", FmOpts), ("lanczos", LanczosOpts)]
+
+
+_ML_LEVEL_FIELDS = ("nodes", "nets", "pins", "match_rounds", "match_pairs", "cut_before", "cut_after", "fm_moves")
+_ML_INTS = ("sweep_feasible", "max_cluster", "total_weight", "max_part", "cut", "cut_nets", "w0", "w1", "n0", "n1")
+_ML_TIMES = ("t_match", "t_contract", "t_lanczos", "t_sweep", "t_fm", "t_total")
+
+
+class MlResult(_AbiStruct):
+    """eigkl.h ek_ml_result (the multilevel bipartition)."""
+    _fields_ = ([("levels", _I32), ("coarsest_fallback", _I32)]
+                + [(k, _I64 * (ML_LEVELS + 1)) for k in _ML_LEVEL_FIELDS] + [(k, _I64) for k in _ML_INTS]
+                + [(k, ctypes.c_double) for k in _ML_TIMES])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -289,6 +320,14 @@ _sig("ek_fm_refine_w_host", ctypes.c_int, _P, ctypes.POINTER(FmOpts), _P, _P, _I
      ctypes.POINTER(FmWResult))
 _sig("ek_fm_refine_w", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _I64, _P, _I64,
      ctypes.POINTER(FmWResult))
+_sig("ek_match_default_opts", None, ctypes.POINTER(MatchOpts))
+_sig("ek_match_host", ctypes.c_int, _P, ctypes.POINTER(MatchOpts), _P, _P, _P, _I64, ctypes.POINTER(MatchResult))
+_sig("ek_match", ctypes.c_int, _P, _P, ctypes.POINTER(MatchOpts), _P, _P, _P, _I64, ctypes.POINTER(MatchResult))
+_sig("ek_hgr_contract", ctypes.c_int, _P, _P, _I64, ctypes.POINTER(_P))
+_sig("ek_ml_default_opts", None, ctypes.POINTER(MlOpts))
+_sig("ek_multilevel_bipartition", ctypes.c_int, _P, _P, ctypes.POINTER(MlOpts), _P, ctypes.POINTER(MlResult))
+_sig("ek_multilevel_bipartition_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(MlOpts), ctypes.c_char_p, _P,
+     ctypes.POINTER(MlResult))
 
 lib = _lib
 
@@ -443,6 +482,19 @@ class Hypergraph:
         m = np.empty(self.nodes, np.int32)
         _chk(_lib.ek_hgr_induce(self._h, _p(keep), ctypes.byref(c), _p(m)), "induce")
         return Hypergraph(c), m
+
+    def contract(self, cluster, n_coarse=None):
+        """The contraction along cluster, a map of the nodes onto [0, n_coarse) that hits every value
+        (ek_hgr_contract): cluster weights summed, nets mapped and made distinct, those left with fewer than 2 pins
+        dropped, nets of one pin set merged with their weights summed.  n_coarse: max(cluster) + 1 by default."""
+        cluster = np.ascontiguousarray(cluster, np.int32)
+        if len(cluster) != self.nodes:
+            raise ValueError(f"cluster has {len(cluster)} entries for {self.nodes} nodes")
+        if n_coarse is None:
+            n_coarse = int(cluster.max()) + 1 if len(cluster) else 0
+        c = _P()
+        _chk(_lib.ek_hgr_contract(self._h, _p(cluster), int(n_coarse), ctypes.byref(c)), "contract")
+        return Hypergraph(c)
 
     def laplacian(self):
         """fp64 clique Laplacian (cEIG.cpp:86-133)."""
@@ -669,6 +721,52 @@ def fm_refine_w_host(hgr, side, imbalance=0.03, max_passes=0, stall=1000, move_c
     move_log, result dict): a move's gain and cut are weighted, a pass_log row ends with |S0 - S1|."""
     return _fm_refine(lambda *a: _lib.ek_fm_refine_w_host(hgr._h, *a), "fm_refine_w_host", hgr, side, imbalance,
                       max_passes, stall, move_cap, FmWResult)
+
+
+def _match(call, what, hgr, max_cluster, max_net, max_rounds):
+    """(mate, cluster, round log, result dict): the log has one row per round that matched, (proposers, pairs)."""
+    o = MatchOpts()
+    _lib.ek_match_default_opts(ctypes.byref(o))
+    o.max_net, o.max_rounds, o.max_cluster = int(max_net), int(max_rounds), int(max_cluster)
+    n = hgr.nodes
+    cap = int(max_rounds) if max_rounds > 0 else 64
+    while True:
+        mate = np.full(n, -2, np.int32)
+        cluster = np.full(n, -2, np.int32)
+        log = np.zeros((cap, 2), np.int64)
+        r = MatchResult()
+        _chk(call(ctypes.byref(o), _p(mate), _p(cluster), _p(log), cap, ctypes.byref(r)), what)
+        if r.rounds <= cap:  # (else: deterministic, so the same run again with room for its log)
+            break
+        cap = r.rounds
+    res = {name: getattr(r, name) for name, _ in MatchResult._fields_ if name != "pad"}
+    return mate, cluster, log[:r.rounds].copy(), res
+
+
+def match_host(hgr, max_cluster=2, max_net=64, max_rounds=8):
+    """The heavy-edge matching of the coarsening on the host (ek_match_host, the checker of Context.match): pairs
+    that propose to each other over their best shared net of at most max_net pins, their weights summing to at most
+    max_cluster.  Returns (mate, cluster, round log, result dict): mate[v] the partner or -1, cluster[v] the rank of
+    v's cluster among the clusters' least ids."""
+    return _match(lambda *a: _lib.ek_match_host(hgr._h, *a), "match_host", hgr, max_cluster, max_net, max_rounds)
+
+
+def _ml_opts(imbalance, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos):
+    o = MlOpts()
+    _lib.ek_ml_default_opts(ctypes.byref(o))
+    o.imbalance, o.coarse_nodes, o.max_levels = float(imbalance), int(coarse_nodes), int(max_levels)
+    o.match.max_cluster, o.match.max_net, o.match.max_rounds = int(max_cluster), int(max_net), int(max_rounds)
+    o.fm.max_passes, o.fm.stall = int(max_passes), int(stall)
+    for name, val in (lanczos or {}).items():
+        setattr(o.lanczos, name, val)
+    return o
+
+
+def _ml_result(r):
+    out = {k: getattr(r, k) for k in ("levels", "coarsest_fallback") + _ML_INTS + _ML_TIMES}
+    for k in _ML_LEVEL_FIELDS:
+        out[k] = list(getattr(r, k))[:r.levels + 1]
+    return out
 
 
 def eig_write(path, lam, median, bits, v):
@@ -982,6 +1080,35 @@ class Context:
         round log.  Returns (part, result dict, round log)."""
         return _kway_refine(lambda *a: _lib.ek_kway_refine(self._c, hgr._h, *a), "kway_refine", hgr, part, k,
                             imbalance, max_rounds)
+
+    def match(self, hgr, max_cluster=2, max_net=64, max_rounds=8):
+        """match_host on the GPU (ek_match): the same mate, cluster, round log and result integers."""
+        return _match(lambda *a: _lib.ek_match(self._c, hgr._h, *a), "match", hgr, max_cluster, max_net, max_rounds)
+
+    def multilevel_bipartition(self, hgr, imbalance=0.03, coarse_nodes=512, max_levels=ML_LEVELS, max_cluster=0,
+                               max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None):
+        """The multilevel bipartition (ek_multilevel_bipartition): matching and contraction down to coarse_nodes
+        nodes, the weighted sweep cut of the coarsest level's Fiedler vector, the weighted FM refinement at every
+        level.  max_cluster 0: from W, L_max and coarse_nodes.  lanczos: ek_lanczos_opts fields to override.
+        Returns (side per node, result dict); the per-level lists of the dict hold levels + 1 entries."""
+        o = _ml_opts(imbalance, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos)
+        side = np.full(hgr.nodes, 255, np.uint8)
+        r = MlResult()
+        _chk(_lib.ek_multilevel_bipartition(self._c, hgr._h, ctypes.byref(o), _p(side), ctypes.byref(r)),
+             "multilevel_bipartition")
+        return side, _ml_result(r)
+
+    def multilevel_bipartition_file(self, path, imbalance=0.03, coarse_nodes=512, out_dir=None, max_levels=ML_LEVELS,
+                                    max_cluster=0, max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None):
+        """The same on the hMETIS reading of a file, written to results/<base>.part.2 under out_dir
+        (ek_multilevel_bipartition_file).  Returns (side per node, result dict)."""
+        o = _ml_opts(imbalance, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos)
+        side = np.full(Hypergraph.read_weighted(path).nodes, 255, np.uint8)
+        r = MlResult()
+        _chk(_lib.ek_multilevel_bipartition_file(self._c, os.fsencode(path), ctypes.byref(o),
+                                                 os.fsencode(out_dir) if out_dir else None, _p(side), ctypes.byref(r)),
+             f"multilevel_bipartition_file {path}")
+        return side, _ml_result(r)
 
     def partition_kway_file(self, path, k, min_spectral=32, limit=-1, write_results=True, out_dir=None,
                             lanczos=None):

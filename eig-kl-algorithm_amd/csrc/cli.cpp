@@ -63,6 +63,14 @@
 //   --no-kl              with --sweep-weighted: no KL graph and no KL loop (KL
 //                        swaps pairs and ignores weights, so it can leave the
 //                        bound); the sweep's sides go straight to ek_fm_refine_w
+//   --multilevel EPS     gKL2 <in.hgr> -EIG only, not with --k, --sweep or --fm:
+//                        the multilevel bipartition (ek_multilevel_bipartition_file)
+//                        with imbalance EPS on the hMETIS reading of the file:
+//                        matching and contraction down to --ml-coarse N nodes
+//                        (default 512), the weighted sweep cut of the coarsest
+//                        level's Fiedler vector, the weighted FM refinement at
+//                        every level (--fm-passes, --fm-stall apply) ->
+//                        results/<base>.part.2; one line beginning "ml:"
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -109,6 +117,10 @@ int fmw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int
 int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, double sweep_eps, int no_kl,
                         double imbalance, int max_passes, int stall, ek_sweep_w_result* sr, ek_kl_result* kr,
                         ek_fm_w_result* fr) __attribute__((weak));
+// multilevel.cpp: ek_multilevel_bipartition_file, for `--multilevel EPS`
+// (coarse_nodes <= 0, stall < 0: the defaults)
+int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, double imbalance, int coarse_nodes,
+                    int max_passes, int stall, ek_ml_result* r) __attribute__((weak));
 }
 
 namespace {
@@ -128,6 +140,9 @@ struct Opts {
     int fm_passes = 0, fm_stall = -1;  // (-1: the default)
     bool weighted = false;             // --weighted
     bool sweep_weighted = false, no_kl = false;  // --sweep-weighted, --no-kl
+    bool ml = false, ml_sub = false;  // --multilevel EPS; --ml-coarse seen
+    double ml_eps = 0.0;
+    int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
     int reorth = 0;  // 0: default (partial)
     double tol = 0.0;
@@ -429,6 +444,31 @@ int run_fm(const Opts& o) {
     return 0;
 }
 
+constexpr const char* ML_USAGE =
+    "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> [--ml-coarse <N>] [--fm-passes <P>] [--fm-stall <S>]  "
+    "(--multilevel needs gKL2 and -EIG, and excludes --k, --sweep and --fm; --ml-coarse needs --multilevel; the file "
+    "is read as hMETIS reads it)\n";
+
+// gKL2 <in.hgr> -EIG --multilevel EPS: one summary line beginning "ml:", results/<base>.part.2
+int run_ml(const Opts& o) {
+    const auto t0 = clk::now();
+    CtxInit ci(o.device, o.teardown);
+    const ek_solve_opts so = solve_opts(o);
+    if (!ek::ml_file_for_cli) throw Fail{"this build carries no multilevel path"};
+    ek_ml_result r{};
+    check(ek::ml_file_for_cli(ci.get(), o.input.c_str(), &so.lanczos, o.ml_eps, o.ml_coarse, o.fm_passes, o.fm_stall, &r),
+          "multilevel bipartition");
+    std::printf("ml: imbalance %g, levels %d, coarsest_nodes %lld, max_cluster %lld, fallback %d, feasible %lld, "
+                "coarsest_cut %lld, cut %lld, cut_nets %lld, w0 %lld, w1 %lld, total_weight %lld, max_part %lld, n0 %lld, "
+                "n1 %lld, %.3f s (match %.3f, contract %.3f, lanczos %.3f, sweep %.3f, fm %.3f), %.3f s -> "
+                "results/%s.part.2\n", o.ml_eps, r.levels, (long long)r.nodes[r.levels], (long long)r.max_cluster,
+                r.coarsest_fallback, (long long)r.sweep_feasible, (long long)r.cut_before[r.levels], (long long)r.cut,
+                (long long)r.cut_nets, (long long)r.w0, (long long)r.w1, (long long)r.total_weight, (long long)r.max_part,
+                (long long)r.n0, (long long)r.n1, r.t_total, r.t_match, r.t_contract, r.t_lanczos, r.t_sweep, r.t_fm,
+                secs(t0), base_name(o.input).c_str());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ek_cli_main(const char* tool_c, int argc, char** argv) {
@@ -486,6 +526,15 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             else if (a == "--weighted") o.weighted = true;
             else if (a == "--sweep-weighted") o.sweep_weighted = true;
             else if (a == "--no-kl") o.no_kl = true;
+            else if (a == "--multilevel") {
+                o.ml_eps = std::stod(need("--multilevel"));
+                o.ml = true;
+                if (!std::isfinite(o.ml_eps) || o.ml_eps < 0) throw Fail{"--multilevel takes an imbalance >= 0"};
+            } else if (a == "--ml-coarse") {
+                o.ml_coarse = std::stoi(need("--ml-coarse"));
+                o.ml_sub = true;
+                if (o.ml_coarse < 1) throw Fail{"--ml-coarse takes a node count of at least 1"};
+            }
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");
@@ -497,14 +546,27 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         } catch (const Fail& e) {
             std::fprintf(stderr, "Error: %s\n", e.msg.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
+            if (a.rfind("--m", 0) == 0) std::printf("%s", ML_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
+            if (a.rfind("--m", 0) == 0) std::printf("%s", ML_USAGE);
             return 1;
         }
     }
     try {
+        if (o.ml || o.ml_sub) {
+            if (!o.ml || o.kway || o.refine || o.sweep || o.sweep_ratio || o.fm || o.weighted || o.sweep_weighted ||
+                o.no_kl || o.tool != "gKL2" || !(pos.size() == 2 && pos[1] == "-EIG")) {
+                std::printf("%s", ML_USAGE);
+                return 1;
+            }
+            mkdirs();
+            o.input = pos[0];
+            o.eig = true;
+            return run_ml(o);
+        }
         if ((o.sweep_weighted || o.no_kl) &&
             (!o.sweep_weighted || !o.sweep || !o.fm || !o.weighted || o.sweep_ratio || o.kway || o.tool != "gKL2" ||
              !(pos.size() == 2 && pos[1] == "-EIG"))) {

@@ -209,13 +209,23 @@ ek_fm_opts fm_check(const char* who, const ek_hgr* h, const ek_fm_opts* opts, co
 // input.  fm_check, then refine_prepare with c(e) of every participating net
 // and w(v) of every node (1 where h has no such array), W, L_max = floor((1 +
 // imbalance) ceil(W / 2)) and the range rules of eigkl.h (EK_EINVAL)
-struct FmwInput {
+struct WeightedInput {
     RefineInput in;
     std::vector<int32_t> cw, w;  // per participating net; per node
+};
+struct FmwInput : WeightedInput {
     int64_t total = 0, max_part = 0;
     ek_fm_opts opts;
 };
 void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side, FmwInput& out);
+// the part of it that needs no sides (the matching shares it): refine_prepare,
+// cw, w and the range rules; returns W
+int64_t weights_prepare(const char* who, const ek_hgr* h, WeightedInput& out);
+
+// match.cpp — what the host and the device matching share: the argument checks
+// (EK_EINVAL as eigkl.h lists it; the opts with the defaults filled in) and the
+// input, weights_prepare's
+ek_match_opts match_check(const char* who, const ek_hgr* h, const ek_match_opts* opts, WeightedInput& in);
 }  // namespace ek
 
 // ---------------------------------------------------------------------------
@@ -867,6 +877,29 @@ void fm_pass(hipStream_t s, const D& d, int stall, long long mlog_at, long long*
 // moves first .. first + count - 1 of pass_nodes flipped back, the counts (weighted: and state[1..2]) with them
 template <class D>
 void fm_rollback(hipStream_t s, const D& d, int first, int count);
+
+// kernels_match.hip — the matching (ek_match)
+constexpr int MATCH_THREADS = 256;  // a workgroup of the node kernels
+constexpr int MATCH_SHORT = 32;     // up to this many entries a node is its thread's, above it its wave's
+struct MatchDev {
+    int n, nets, max_net;
+    long long cap;                     // max_cluster
+    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
+    const int32_t *pins, *inc, *cw, *w;
+    long long* score;  // per net: score(e), -1 when the net is not eligible
+    int32_t* entries;  // per node: its pins' count over its eligible nets, itself excluded (capped at INT32_MAX)
+    int32_t *mate, *prop;
+    int* flag;                // n: 1 for a leader
+    long long *rank, *tiles;  // n + 1: the flags' exclusive scan; its scratch, (n + 1023) / 1024
+    int32_t* cluster;
+};
+// score[] and entries[] from the nets and weights; *eligible (device, zero before) = the eligible nets.  nets > 0.
+void match_prepare(hipStream_t s, const MatchDev& d, unsigned long long* eligible);
+// one round: prop[] from mate[], then the mutual proposals into mate[].
+// slot (device, zero before): the round's proposers and pairs
+void match_round(hipStream_t s, const MatchDev& d, unsigned long long* slot);
+// cluster[] of mate[]; rank[n] = the clusters
+void match_cluster(hipStream_t s, const MatchDev& d);
 
 }  // namespace dev
 }  // namespace ek

@@ -3,7 +3,8 @@
 //
 // fmw_prepare is all that the weighted checker and the weighted device path
 // (fm.cpp, ctx_fm.cpp) share; ek_fm_refine_host and ek_fm_refine never call
-// it and ignore the weights.  ek_bipart_metrics_host is written apart from
+// it and ignore the weights.  Its part that needs no sides, weights_prepare,
+// is also the matching's input (match.cpp).  ek_bipart_metrics_host is written apart from
 // the FM code: it walks the hypergraph's own pins, not the prepared input.
 #include <algorithm>
 #include <vector>
@@ -16,8 +17,7 @@ constexpr int64_t W_LIMIT = int64_t(1) << 62;  // of W and of the sum of all c(e
 
 namespace ek {
 
-void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side, FmwInput& out) {
-    out.opts = fm_check(who, h, opts, side);
+int64_t weights_prepare(const char* who, const ek_hgr* h, WeightedInput& out) {
     refine_prepare(*h, out.in);
     const int64_t n = h->nodes, nets = int64_t(out.in.net_ptr.size()) - 1;
     // c(e) of the participating nets: refine_prepare keeps, in file order, the nets of >= 2 distinct pins
@@ -58,8 +58,13 @@ void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const
             fail(EK_EINVAL, "%s: the nets on node %lld weigh %lld (at most 2^31 - 1: gains are int32)", who, (long long)v,
                  (long long)on);
     }
-    out.total = total;
-    out.max_part = refine_max_part(total, 2, out.opts.imbalance);
+    return total;
+}
+
+void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side, FmwInput& out) {
+    out.opts = fm_check(who, h, opts, side);
+    out.total = weights_prepare(who, h, out);
+    out.max_part = refine_max_part(out.total, 2, out.opts.imbalance);
 }
 
 }  // namespace ek

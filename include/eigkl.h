@@ -842,6 +842,115 @@ int ek_fm_refine_w(ek_ctx* ctx, const ek_hgr* h, const ek_fm_opts* opts, uint8_t
                    ek_fm_w_result* result);
 
 /* ------------------------------------------------------------------ */
+/* Coarsening: a heavy-edge matching, the contraction it defines, and   */
+/* the multilevel bipartition over them.  No reference counterpart.     */
+/* ------------------------------------------------------------------ */
+/* The matching rule, all integers, every tie broken by ids.
+ * The input is the FM rules': the nets with at least 2 distinct pins, each pin
+ * once; w(v) and c(e) of h, 1 where h carries no such array.  Net e is
+ * eligible iff its distinct size |e| <= max_net; score(e) = floor(c(e) 2^20 /
+ * (|e| - 1)), int64.  Every node starts unmatched (mate -1).
+ * One round, all of it read from the state at the round's start: (1) every
+ * unmatched u looks at the entries (e, v) with e eligible, u and v pins of e,
+ * v != u, v unmatched and w(u) + w(v) <= max_cluster; p(u) is the v of the
+ * entry of greatest (score(e), then smaller v), -1 without an entry.  A pair's
+ * score is that of its best shared net, not a sum over its shared nets.  (2) u
+ * and v are matched iff p(u) = v and p(v) = u.
+ * The run ends with the first round that matches nothing (not counted, not
+ * logged) or after max_rounds rounds.  While a feasible pair exists a round
+ * matches one (the entry of greatest score whose smaller id is least proposes
+ * both ways), so max_rounds <= 0 ends at a maximal matching.
+ * The cluster of a node is itself and its mate; the cluster's leader is its
+ * least id; cluster[v] = the rank of v's leader among all leaders in ascending
+ * id order; n_coarse = the number of leaders. */
+typedef struct {
+    int32_t max_net;     /* default 64; values below 2 act as 2 */
+    int32_t max_rounds;  /* default 8; <= 0: until a round matches nothing */
+    int64_t max_cluster; /* the greatest w(u) + w(v) of a pair; >= 1 (ek_match_default_opts: 2) */
+} ek_match_opts;
+
+typedef struct {
+    int64_t n, n_coarse, pairs; /* nodes; clusters; matched pairs = n - n_coarse */
+    int32_t rounds, pad;        /* rounds that matched at least one pair */
+    int64_t eligible_nets;
+    double t_setup, t_rounds;   /* wall seconds (host clock) */
+} ek_match_result;
+
+void ek_match_default_opts(ek_match_opts* o);
+/* The matching on the host (no GPU): the checker of ek_match, single threaded
+ * and written from the rule.  mate_out and cluster_out: one value per node of
+ * h, either may be NULL.  round_log (may be NULL) receives two values per
+ * round, for the first log_rounds rounds: proposers (p(u) >= 0) and pairs.
+ * EK_EINVAL for max_cluster < 1, more than INT32_MAX - 1 nodes, and the weight
+ * ranges of ek_fm_refine_w. */
+int ek_match_host(const ek_hgr* h, const ek_match_opts* opts, int32_t* mate_out, int32_t* cluster_out,
+                  int64_t* round_log, int64_t log_rounds, ek_match_result* result);
+/* The same on the GPU: the same mate, cluster, round log and result integers.
+ * Two launches a round; the host reads one 8-byte counter per round.
+ * EK_ESTATE on a multi-rank context.  Every buffer is local to the call and
+ * the context keeps nothing. */
+int ek_match(ek_ctx* ctx, const ek_hgr* h, const ek_match_opts* opts, int32_t* mate_out, int32_t* cluster_out,
+             int64_t* round_log, int64_t log_rounds, ek_match_result* result);
+/* The contraction of h along cluster (host only): any map of h's nodes onto
+ * [0, n_coarse) that hits every value.  A coarse node weighs the sum of its
+ * nodes' w(v).  Every net of h, in file order, is mapped through cluster, its
+ * pins made distinct in first-occurrence order; a net left with fewer than 2
+ * pins is dropped; nets with the same pin set merge into the first of them,
+ * their c(e) summed.  The result always carries both weight arrays.  The
+ * weighted cut and the side weights of any coarse side vector s' equal those
+ * of s'(cluster(.)) on h (ek_bipart_metrics_host out[0], out[2], out[3]; the
+ * cut NETS differ: merged nets count once).  EK_EINVAL for
+ * a cluster id outside [0, n_coarse), an id no node maps to, or a summed
+ * weight above INT32_MAX. */
+int ek_hgr_contract(const ek_hgr* h, const int32_t* cluster /* nodes */, int64_t n_coarse, ek_hgr** out);
+
+/* The multilevel bipartition.  H_0 = h.  While H_l holds more
+ * than coarse_nodes nodes and l < max_levels: ek_match, then ek_hgr_contract;
+ * the new level is dropped and coarsening ends when it shrinks by less than
+ * 10 % (10 n_(l+1) > 9 n_l).  On the coarsest H_L: ek_spmv_setup_pins,
+ * ek_lanczos_fiedler, ek_sweep_cut_w at `imbalance`, sides = ek_rank_split(v,
+ * n1); without a net of >= 2 pins, below the nodes ek_lanczos_fiedler accepts,
+ * or on EK_ENOCONV, v[i] = -i instead (coarsest_fallback = 1).  Then
+ * ek_fm_refine_w on H_L, and for l = L - 1 .. 0 the sides projected through
+ * cluster_l and ek_fm_refine_w on H_l.  No KL: it swaps pairs and ignores
+ * weights.  Lanczos sees the coarse structure only, not its weights. */
+#define EK_ML_LEVELS 32 /* the most coarse levels; the per-level arrays also hold the input, level 0 */
+typedef struct {
+    double imbalance;     /* epsilon >= 0; default 0.03; overwrites fm.imbalance */
+    int32_t coarse_nodes; /* coarsening stops at this many nodes; default 512; values below 8 act as 8 */
+    int32_t max_levels;   /* default and maximum EK_ML_LEVELS; values outside [1, EK_ML_LEVELS] act as it */
+    ek_match_opts match;  /* max_cluster <= 0 (default): max(1, min(2 L_max - W + 1, ceil(4 W / coarse_nodes))),
+                           * the first term being the condition under which ek_sweep_cut_w has a feasible split */
+    ek_fm_opts fm;
+    ek_lanczos_opts lanczos;
+} ek_ml_opts;
+
+typedef struct {
+    int32_t levels;            /* L: the coarse levels kept; level l of the arrays below is H_l, 0 <= l <= L */
+    int32_t coarsest_fallback; /* 1: the coarsest split came from v[i] = -i */
+    int64_t nodes[EK_ML_LEVELS + 1], nets[EK_ML_LEVELS + 1], pins[EK_ML_LEVELS + 1];
+    int64_t match_rounds[EK_ML_LEVELS + 1], match_pairs[EK_ML_LEVELS + 1]; /* of the matching H_l -> H_(l+1), l < L */
+    int64_t cut_before[EK_ML_LEVELS + 1], cut_after[EK_ML_LEVELS + 1];     /* weighted cut around H_l's FM */
+    int64_t fm_moves[EK_ML_LEVELS + 1];                                    /* moves that FM kept */
+    int64_t sweep_feasible;    /* the coarsest sweep's `feasible` */
+    int64_t max_cluster;       /* the matching's bound as used */
+    int64_t total_weight, max_part;  /* W; L_max = floor((1 + imbalance) ceil(W / 2)) */
+    int64_t cut, cut_nets, w0, w1, n0, n1; /* ek_bipart_metrics_host of side_out on h, and the sides' node counts */
+    double t_match, t_contract, t_lanczos, t_sweep, t_fm, t_total; /* wall seconds (host clock) */
+} ek_ml_result;
+
+void ek_ml_default_opts(ek_ml_opts* o);
+/* side_out: one byte in {0, 1} per node of h.  EK_ESTATE on a multi-rank
+ * context; EK_EINVAL as the entries it calls.  result may be NULL. */
+int ek_multilevel_bipartition(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* opts, uint8_t* side_out /* nodes */,
+                              ek_ml_result* result);
+/* The same on the hMETIS reading of a file (ek_hgr_read_weighted), written to
+ * results/<base>.part.2 under out_dir (NULL: the CWD), one side per line in
+ * node order.  side_out may be NULL. */
+int ek_multilevel_bipartition_file(ek_ctx* ctx, const char* path, const ek_ml_opts* opts, const char* out_dir,
+                                   uint8_t* side_out, ek_ml_result* result);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
