@@ -111,7 +111,7 @@ int fm_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int 
 int fmw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, int sweep, double sweep_eps, int ratio,
                      double imbalance, int max_passes, int stall, ek_sweep_result* sr, ek_kl_result* kr,
                      ek_fm_w_result* fr) __attribute__((weak));
-// sweepw.cpp: the weighted sweep split (no_kl: without the KL loop), then ek_fm_refine_w, for
+// sweep.cpp: the weighted sweep split (no_kl: without the KL loop), then ek_fm_refine_w, for
 // `--sweep EPS --sweep-weighted --fm EPS --weighted [--no-kl]`
 // (stall < 0: the default)
 int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, double sweep_eps, int no_kl,

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <utility>
@@ -187,16 +188,23 @@ struct RefineInput {
 };
 void refine_prepare(const ek_hgr& h, RefineInput& in);
 
-// sweep.cpp — what the host and the device sweep cut share: the argument
-// checks (EK_EINVAL as eigkl.h lists it; the opts with the defaults filled
-// in) and the balance window (n, max_part, s_lo, s_hi of the result)
+// the order of the rank split and of the sweep cuts, on the host: ascending
+// ord_key(v) is ascending v with -0 before +0 (the device's ord_key,
+// kernels_kl.hip, rank_key and sweep_key)
+inline uint64_t ord_key(double v) {
+    uint64_t u;
+    std::memcpy(&u, &v, 8);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// sweep.cpp — what the host and the device sweep cuts share.  The count
+// sweep: the argument checks (EK_EINVAL as eigkl.h lists it; the opts with the
+// defaults filled in) and the balance window (n, max_part, s_lo, s_hi of the
+// result).  The weighted sweep: the argument checks (sweep_check's, objective
+// 1 refused, every w(v) >= 0 and c(e) >= 1, W and the sum of c(e) at most
+// 2^62) and n, W, L_max = refine_max_part(W, 2, imbalance) of the result
 ek_sweep_opts sweep_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts);
 void sweep_window(int64_t n, double imbalance, ek_sweep_result& r);
-
-// sweepw.cpp — what the host and the device weighted sweep cut share: the
-// argument checks (sweep_check's, objective 1 refused, every w(v) >= 0 and
-// c(e) >= 1, W and the sum of c(e) at most 2^62) and n, W, L_max =
-// refine_max_part(W, 2, imbalance) of the result
 ek_sweep_opts sweepw_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts,
                            ek_sweep_w_result& r);
 
@@ -776,9 +784,12 @@ struct RefineDev {
 // candidates, accepted moves and gain.  nets > 0.
 void refine_round(hipStream_t s, const RefineDev& d, unsigned long long* slot);
 
-// kernels_sweep.hip — the sweep cut (ek_sweep_cut): sort, profile, choice
+// kernels_sweep.hip — the sweep cuts (ek_sweep_cut, ek_sweep_cut_w): sort,
+// scans, the count and the weighted profile, prefix weights, the two choices
 constexpr int SWEEP_TILE = 2048;                // keys per workgroup of a sort pass
-constexpr int SWEEP_SELECT_MAX_BLOCKS = 1024;   // partials of the choice
+constexpr int SWEEP_SCAN_BLOCK = 2048;          // words per workgroup of a scan, of either width
+constexpr int SWEEP_SELECT_MAX_BLOCKS = 1024;   // partials of a choice
+constexpr int SWEEPW_REC = 10;                  // words of the weighted choice's result record
 int sweep_tiles(int n);
 // keys[i] = ord(v[i]), ids[i] = i; ghist (8 x 256 words, zero before): the
 // keys per digit of each of the 8 passes
@@ -789,40 +800,31 @@ void sweep_sort_pass(hipStream_t s, int n, int pass, const unsigned long long* k
                      unsigned long long* keys_out, int32_t* ids_out, unsigned* table, unsigned* scan_tmp);
 // pos[order[r]] = r
 void sweep_pos(hipStream_t s, const int32_t* order, int n, int32_t* pos);
-// prefix sum of data[0:count) in place, modulo 2^32 (exclusive or inclusive)
+// prefix sum of data[0:count) in place, exclusive or inclusive, modulo 2^32
+// (T = unsigned) or 2^64 (T = unsigned long long); tmp:
+// sweep_scan_tmp_words(count) words of T.  Any count below 2^31 (see the
+// kernels).
 size_t sweep_scan_tmp_words(long long count);
-void sweep_scan(hipStream_t s, unsigned* data, long long count, bool inclusive, unsigned* tmp);
+template <class T>
+void sweep_scan(hipStream_t s, T* data, long long count, bool inclusive, T* tmp);
 // diff (n + 1 words, zero before): +1 at lo + 1, -1 at hi + 1 of every net
 // with lo < hi; span_part[b]: those nets per workgroup, sweep_span_blocks(nets)
+// words.  diffw not null, the weighted profile too (n + 1 int64 words, zero
+// before): +c(e) at lo + 1, -c(e) at hi + 1 of the same nets (cw null: c = 1)
 int sweep_span_blocks(int64_t nets);
 void sweep_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* pos, int n,
-                 unsigned* diff, unsigned* span_part);
-// rec[0..3] = s*, profile[s*], profile[n / 2], sum of span_part[0:nspan);
-// part: 2 * sweep_select_blocks(window) words
+                 unsigned* diff, unsigned* span_part, const int32_t* cw, unsigned long long* diffw);
+// the count sweep's choice: rec[0..3] = s*, profile[s*], profile[n / 2], sum
+// of span_part[0:nspan); part: 2 * sweep_select_blocks(window) words
 int sweep_select_blocks(int64_t window);
 void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, int64_t s_hi, int objective,
                   unsigned* part, const unsigned* span_part, int nspan, long long* rec);
-
-// kernels_sweepw.hip — the weighted sweep cut (ek_sweep_cut_w): the sort, pos
-// and the count profile's scan are kernels_sweep.hip's
-constexpr int SWEEPW_SCAN_BLOCK = 2048;  // 64-bit words per workgroup of the scan
-constexpr int SWEEPW_SCAN_TOP = 256;     // block sums per step of the top scan's one workgroup
-constexpr int SWEEPW_REC = 10;           // words of the result record
-// diffw (n + 1 int64 words, zero before): +c(e) at lo + 1, -c(e) at hi + 1 of
-// every net with lo < hi (cw null: c = 1); diff (n + 1 words, zero before) and
-// span_part (sweep_span_blocks(nets) words) as sweep_spans
-void sweepw_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* cw,
-                  const int32_t* pos, int n, unsigned long long* diffw, unsigned* diff, unsigned* span_part);
 // pw[0] = 0, pw[r + 1] = w[order[r]] (w null: 1): its inclusive scan is P
 void sweepw_gather(hipStream_t s, const int32_t* order, const int32_t* w, int n, unsigned long long* pw);
-// inclusive prefix sum of data[0:count) in place, modulo 2^64; tmp:
-// sweepw_scan_tmp_words(count) words.  Any count below 2^31 (see the kernels).
-size_t sweepw_scan_tmp_words(long long count);
-void sweepw_scan(hipStream_t s, unsigned long long* data, long long count, unsigned long long* tmp);
-// the choice over s = 1 .. n - 1 from profile_w and P (n + 1 words each), W
-// and L_max; part: 5 * sweepw_select_blocks(n) words.  rec[0..9] = s* (-1:
-// none), feasible, s_lo, s_hi, profile_w[s*], profile[s*], profile_w[n / 2],
-// the sum of span_part[0:nspan), P[s*], P[n]
+// the weighted sweep's choice over s = 1 .. n - 1 from profile_w and P (n + 1
+// words each), W and L_max; part: 5 * sweepw_select_blocks(n) words.
+// rec[0..9] = s* (-1: none), feasible, s_lo, s_hi, profile_w[s*], profile[s*],
+// profile_w[n / 2], the sum of span_part[0:nspan), P[s*], P[n]
 int sweepw_select_blocks(int n);
 void sweepw_select(hipStream_t s, const unsigned long long* profw, const unsigned long long* prefix,
                    const unsigned* profile, int n, unsigned long long total, unsigned long long max_part,

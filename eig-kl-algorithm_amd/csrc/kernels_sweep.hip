@@ -1,17 +1,24 @@
-// Sweep cut of a Fiedler vector (ctx_sweep.cpp; the rule: eigkl.h, DESIGN.md
-// §10): a stable radix sort of the nodes by (ord(v), id), the net-cut profile
-// of every prefix split, and the choice of the best split inside the balance
-// window.  A translation unit of its own: the code objects of the
-// bipartitioner's kernels are what they were without it.
+// The sweep cuts of a Fiedler vector (ctx_sweep.cpp; the rules: eigkl.h,
+// DESIGN.md §10 and §13): a stable radix sort of the nodes by (ord(v), id),
+// the net-cut profile of every prefix split, in net counts and in net weights,
+// the prefix weight of every split, and the two choices: the best split inside
+// the count sweep's balance window, and the weighted sweep's best split among
+// those whose two sides weigh at most L_max.  A translation unit of its own:
+// the code objects of the bipartitioner's kernels are what they were without
+// it.
 //
 // Nothing here waits inside a launch: every kernel reads only what earlier
 // launches on the stream wrote.  Everything is integer work, and no result
 // depends on the order workgroups or atomics arrive in: the only atomics are
-// integer adds into counters (histograms, the difference array), which
-// commute, and positions inside a tile come from ballots and popcounts.
+// integer adds into counters (histograms, the two difference arrays), which
+// commute (modulo 2^32 and 2^64), positions inside a tile come from ballots
+// and popcounts, and each choice is a reduction under a strict total order.
+// Weights and structure are read with plain loads and never written.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "ek_internal.hpp"
 
@@ -155,26 +162,36 @@ __global__ __launch_bounds__(SW_THREADS) void k_sweep_pos(const int32_t* __restr
 }
 
 // ---------------------------------------------------------------------------
-// Prefix sum of 32-bit words (sums modulo 2^32: the difference array's -1 is
-// 0xFFFFFFFF), in place, three launches: the sum of every SC_BLOCK-word block,
-// one workgroup's exclusive scan of those sums, then every block scans its
-// words again from its sum's offset.
-constexpr int SC_THREADS = 256, SC_PER = 8, SC_BLOCK = SC_THREADS * SC_PER, SC_WAVES = SC_THREADS / 64;
+// Prefix sum of 32- or 64-bit words (sums modulo 2^32 or 2^64: a difference
+// array's -1 is all ones), in place, three launches: the sum of every
+// SWEEP_SCAN_BLOCK-word block, one workgroup's exclusive scan of those sums,
+// then every block scans its words again from its sum's offset.
+//
+// The scan of the block sums is one workgroup that walks them SC_THREADS at a
+// step and carries the running total from step to step, so it has no limit of
+// its own: count <= 2^31 - 1 words (n <= 2^31 - 2) are at most 2^20 block
+// sums, 4,096 steps.  Up to SC_THREADS block sums (count <= 524,288) it is a
+// single step and the carry is never used; from 524,289 words on the carry
+// path runs.
+constexpr int SC_THREADS = 256, SC_PER = SWEEP_SCAN_BLOCK / SC_THREADS, SC_WAVES = SC_THREADS / 64;
+static_assert(SWEEP_SCAN_BLOCK % SC_THREADS == 0, "a block is whole rows of the workgroup");
 
-__device__ __forceinline__ unsigned wave_inclusive(unsigned x, int l) {
+template <class T>
+__device__ __forceinline__ T wave_inclusive(T x, int l) {
     for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(x, o, 64);
+        const T y = __shfl_up(x, o, 64);
         if (l >= o) x += y;
     }
     return x;
 }
 
-__global__ __launch_bounds__(SC_THREADS) void k_scan_sums(const unsigned* __restrict__ in, long long count,
-                                                          unsigned* __restrict__ bsum) {
-    __shared__ unsigned ws[SC_WAVES];
+template <class T>
+__global__ __launch_bounds__(SC_THREADS) void k_scan_sums(const T* __restrict__ in, long long count,
+                                                          T* __restrict__ bsum) {
+    __shared__ T ws[SC_WAVES];
     const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * SC_BLOCK;
-    unsigned s = 0u;
+    const long long base = (long long)blockIdx.x * SWEEP_SCAN_BLOCK;
+    T s = 0;
 #pragma unroll
     for (int u = 0; u < SC_PER; ++u) {
         const long long i = base + u * SC_THREADS + t;
@@ -186,44 +203,52 @@ __global__ __launch_bounds__(SC_THREADS) void k_scan_sums(const unsigned* __rest
     if (t == 0) bsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
-__global__ __launch_bounds__(SC_THREADS) void k_scan_top(unsigned* __restrict__ bsum, int nb) {
-    __shared__ unsigned ws[SC_WAVES];
+template <class T>
+__global__ __launch_bounds__(SC_THREADS) void k_scan_top(T* __restrict__ bsum, int nb) {
+    __shared__ T ws[SC_WAVES];
     const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    unsigned carry = 0u;
+    T carry = 0;
     for (int c0 = 0; c0 < nb; c0 += SC_THREADS) {
         const int i = c0 + t;
-        const unsigned x = i < nb ? bsum[i] : 0u;
-        const unsigned inc = wave_inclusive(x, l);
+        const T x = i < nb ? bsum[i] : T(0);
+        const T inc = wave_inclusive(x, l);
         if (l == 63) ws[w] = inc;
         __syncthreads();
-        unsigned before = 0u;
-        for (int q = 0; q < SC_WAVES; ++q) before += q < w ? ws[q] : 0u;
+        T before = 0;
+        for (int q = 0; q < SC_WAVES; ++q) before += q < w ? ws[q] : T(0);
         if (i < nb) bsum[i] = carry + before + inc - x;
         carry += ws[0] + ws[1] + ws[2] + ws[3];
         __syncthreads();
     }
 }
 
-// thread t scans the block's words [t * SC_PER, (t + 1) * SC_PER)
-__global__ __launch_bounds__(SC_THREADS) void k_scan_apply(unsigned* __restrict__ data, long long count,
-                                                           const unsigned* __restrict__ bsum, int inclusive) {
-    __shared__ unsigned ws[SC_WAVES];
+// thread t scans the block's words [t * SC_PER, (t + 1) * SC_PER).  mode: an
+// int, not zero for the inclusive scan, or Inclusive where no caller wants the
+// other (the 64-bit scan): that instantiation loads and selects nothing.
+struct Inclusive {};
+
+template <class T, class Mode>
+__global__ __launch_bounds__(SC_THREADS) void k_scan_apply(T* __restrict__ data, long long count,
+                                                           const T* __restrict__ bsum, Mode mode) {
+    __shared__ T ws[SC_WAVES];
     const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    const long long first = (long long)blockIdx.x * SC_BLOCK + (long long)t * SC_PER;
-    unsigned x[SC_PER], s = 0u;
+    const long long first = (long long)blockIdx.x * SWEEP_SCAN_BLOCK + (long long)t * SC_PER;
+    T x[SC_PER], s = 0;
 #pragma unroll
     for (int u = 0; u < SC_PER; ++u) {
-        x[u] = first + u < count ? data[first + u] : 0u;
+        x[u] = first + u < count ? data[first + u] : T(0);
         s += x[u];
     }
-    const unsigned inc = wave_inclusive(s, l);
+    const T inc = wave_inclusive(s, l);
     if (l == 63) ws[w] = inc;
     __syncthreads();
-    unsigned run = bsum[blockIdx.x] + inc - s;
-    for (int q = 0; q < SC_WAVES; ++q) run += q < w ? ws[q] : 0u;
+    T run = bsum[blockIdx.x] + inc - s;
+    for (int q = 0; q < SC_WAVES; ++q) run += q < w ? ws[q] : T(0);
 #pragma unroll
     for (int u = 0; u < SC_PER; ++u) {
-        const unsigned out = inclusive ? run + x[u] : run;
+        T out;
+        if constexpr (std::is_same_v<Mode, Inclusive>) out = run + x[u];
+        else out = mode ? run + x[u] : run;
         run += x[u];
         if (first + u < count) data[first + u] = out;
     }
@@ -231,32 +256,53 @@ __global__ __launch_bounds__(SC_THREADS) void k_scan_apply(unsigned* __restrict_
 
 // ---------------------------------------------------------------------------
 // Profile: per net the least and greatest rank of its pins, +1 at lo + 1 and
-// -1 at hi + 1 of the difference array (n + 1 words, zero before the launch).
-// Laid out as k_kway_metrics: a thread takes its net when it has at most
-// SP_SHORT pins, the wave takes a longer one with a shuffle min / max.
+// -1 at hi + 1 of the count difference array (n + 1 words, zero before the
+// launch).  Laid out as k_kway_metrics: a thread takes its net when it has at
+// most SP_SHORT pins, the wave takes a longer one with a shuffle min / max.
 // span_part[block] = the block's nets with lo < hi.
+//
+// The weighted sweep's instantiation (W = NetWeights) adds +c(e) at lo + 1 and
+// -c(e) at hi + 1 of the int64 difference array (two's complement: the sums
+// are exact modulo 2^64 and the profile itself is at most the sum of all c(e)
+// <= 2^62); cw null: every c(e) is 1.  The count sweep's (W = NoWeights)
+// carries no weight at all.
 constexpr int SP_THREADS = 256, SP_SHORT = 8;
 
+struct NoWeights {};
+struct NetWeights {
+    const int32_t* cw;
+    u64* diffw;
+};
+
+template <class W>
 __global__ __launch_bounds__(SP_THREADS) void k_sweep_spans(long long nets, const int64_t* __restrict__ net_ptr,
                                                             const int32_t* __restrict__ pins,
                                                             const int32_t* __restrict__ pos, int n,
                                                             unsigned* __restrict__ diff,
-                                                            unsigned* __restrict__ span_part) {
+                                                            unsigned* __restrict__ span_part, W wt) {
+    constexpr bool WT = std::is_same_v<W, NetWeights>;
     __shared__ unsigned ws[SP_THREADS / 64];
     const int t = threadIdx.x, l = t & 63;
     const long long e = blockIdx.x * (long long)SP_THREADS + t;
     unsigned spans = 0u;  // this thread's nets (lane 0: also the wave's long nets)
-    auto emit = [&](int lo, int hi) {
+    auto emit = [&](int lo, int hi, [[maybe_unused]] u64 c) {
         if (lo < hi && lo >= 0 && hi < n) {  // (ranks lie in [0, n): the bounds hold for any pos[] a sort left)
+            if constexpr (WT) {
+                atomicAdd(&wt.diffw[lo + 1], c);
+                atomicAdd(&wt.diffw[hi + 1], 0ull - c);
+            }
             atomicAdd(&diff[lo + 1], 1u);
             atomicAdd(&diff[hi + 1], 0xFFFFFFFFu);
             spans += 1u;
         }
     };
     int64_t p0 = 0, p1 = 0;
+    u64 c = 1ull;  // (read by the weighted instantiation only)
     if (e < nets) {
         p0 = net_ptr[e];
         p1 = net_ptr[e + 1];
+        if constexpr (WT)
+            if (wt.cw) c = u64(wt.cw[e]);
     }
     const bool is_long = p1 - p0 > SP_SHORT;
     if (p1 - p0 >= 2 && !is_long) {
@@ -272,7 +318,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sweep_spans(long long nets, cons
                 hi = max(hi, r[u]);
             }
         }
-        emit(lo, hi);
+        emit(lo, hi, c);
     }
     // the wave's long nets, one after the other (the ballot is wave-uniform)
     u64 todo = __ballot(is_long);
@@ -280,6 +326,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_sweep_spans(long long nets, cons
         const int src = __ffsll(todo) - 1;
         todo &= todo - 1ull;
         const int64_t q0 = __shfl(p0, src, 64), q1 = __shfl(p1, src, 64);
+        u64 qc = 1ull;
+        if constexpr (WT) qc = __shfl(c, src, 64);
         int lo = INT32_MAX, hi = -1;
         for (int64_t p = q0 + l; p < q1; p += 64) {
             const int r = pos[pins[p]];
@@ -290,7 +338,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sweep_spans(long long nets, cons
             lo = min(lo, __shfl_xor(lo, o, 64));
             hi = max(hi, __shfl_xor(hi, o, 64));
         }
-        if (l == 0) emit(lo, hi);
+        if (l == 0) emit(lo, hi, qc);
     }
     for (int o = 32; o > 0; o >>= 1) spans += __shfl_xor(spans, o, 64);
     if (l == 0) ws[t >> 6] = spans;
@@ -298,12 +346,31 @@ __global__ __launch_bounds__(SP_THREADS) void k_sweep_spans(long long nets, cons
     if (t == 0) span_part[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
+// pw[0] = 0 and pw[r + 1] = w(order[r]): the inclusive scan of pw is P.  w
+// null: every w(v) is 1.
+__global__ __launch_bounds__(SP_THREADS) void k_sweepw_gather(const int32_t* __restrict__ order,
+                                                              const int32_t* __restrict__ w, int n,
+                                                              u64* __restrict__ pw) {
+    const long long r = (long long)blockIdx.x * SP_THREADS + threadIdx.x;
+    if (r == 0) pw[0] = 0ull;
+    if (r < n) {
+        const int32_t v = order[r];
+        u64 x = 0ull;
+        if (v >= 0 && v < n) x = w ? u64(w[v]) : 1ull;  // (always, for the order a sort left)
+        pw[r + 1] = x;
+    }
+}
+
 // ---------------------------------------------------------------------------
-// Choice: a reduction of the window's splits under the rule's comparator, a
+// The two choices: each a reduction of the splits under its rule's order, a
 // strict total order (every tie ends in the smaller s), so the order of the
-// reduction does not matter.  Per-workgroup partials, then one workgroup.
+// reduction does not matter.  Per-workgroup partials, then one workgroup,
+// which also adds up span_part.
 constexpr int SL_THREADS = 256;
 constexpr unsigned SL_NONE = 0xFFFFFFFFu;  // no split (s never reaches it: n <= INT32_MAX - 1)
+
+// ---------------------------------------------------------------------------
+// The count sweep's choice, over the window s_lo .. s_hi.
 
 // p s (n - s) as two 64-bit words: p < 2^32, q = s (n - s) < 2^62
 __device__ __forceinline__ void mul_p_q(unsigned p, u64 q, u64& hi, u64& lo) {
@@ -357,6 +424,13 @@ __device__ __forceinline__ void sweep_block_best(unsigned& p, unsigned& s, unsig
         for (int q = 1; q < SL_THREADS / 64; ++q) sweep_pick(p, s, ws[0][q], ws[1][q], n, objective);
 }
 
+// thread t's share of the sum of span_part[0:nspan), the nets with lo < hi
+__device__ __forceinline__ u64 span_share(const unsigned* __restrict__ span_part, int nspan, int t) {
+    u64 spans = 0ull;
+    for (int b = t; b < nspan; b += SL_THREADS) spans += span_part[b];
+    return spans;
+}
+
 __global__ __launch_bounds__(SL_THREADS) void k_sweep_select(const unsigned* __restrict__ profile, unsigned n,
                                                              unsigned s_lo, unsigned s_hi, int objective,
                                                              unsigned* __restrict__ part) {
@@ -382,8 +456,7 @@ __global__ __launch_bounds__(SL_THREADS) void k_sweep_finish(const unsigned* __r
     const int t = threadIdx.x;
     unsigned p = 0u, s = SL_NONE;
     for (int b = t; b < nparts; b += SL_THREADS) sweep_pick(p, s, part[2 * b], part[2 * b + 1], n, objective);
-    u64 spans = 0ull;
-    for (int b = t; b < nspan; b += SL_THREADS) spans += span_part[b];
+    u64 spans = span_share(span_part, nspan, t);
     for (int o = 32; o > 0; o >>= 1) spans += __shfl_xor(spans, o, 64);
     if ((t & 63) == 0) sp[t >> 6] = spans;
     sweep_block_best(p, s, n, objective, ws);  // (its barrier also publishes sp)
@@ -396,18 +469,142 @@ __global__ __launch_bounds__(SL_THREADS) void k_sweep_finish(const unsigned* __r
 }
 
 // ---------------------------------------------------------------------------
+// The weighted sweep's choice: one reduction over the splits s = 1 .. n - 1.
+// A split's key is
+//   feasible:    (profile_w[s],          |2 P[s] - W|, s)
+//   infeasible:  (2^63 + |2 P[s] - W|,   profile_w[s], s)
+// compared lexicographically: a strict total order (every tie ends in s) that
+// places every feasible split before every infeasible one (profile_w <= 2^62
+// and |2 P - W| <= W <= 2^62 leave bit 63 free), so the least key is the
+// rule's s* whether the window is empty or not, and the reduction's shape does
+// not matter.  The same pass carries the least and the greatest feasible s
+// (min / max, which commute): s_lo, s_hi, and feasible = there is one.
+constexpr int SL_WORDS = 5;  // a partial: k1, k2, s, lo, hi
+
+struct Pick {
+    u64 k1, k2;
+    unsigned s;       // SL_NONE: none yet
+    unsigned lo, hi;  // the least / greatest feasible split seen (SL_NONE / 0: none)
+};
+
+__device__ __forceinline__ void pick_merge(Pick& a, u64 k1, u64 k2, unsigned s, unsigned lo, unsigned hi) {
+    if (s != SL_NONE) {
+        const bool first = k1 != a.k1 ? k1 < a.k1 : (k2 != a.k2 ? k2 < a.k2 : s < a.s);
+        if (a.s == SL_NONE || first) {
+            a.k1 = k1;
+            a.k2 = k2;
+            a.s = s;
+        }
+    }
+    a.lo = min(a.lo, lo);
+    a.hi = max(a.hi, hi);
+}
+
+// the workgroup's pick in thread 0
+__device__ __forceinline__ void pick_block(Pick& a, u64 (*wk)[SL_THREADS / 64], unsigned (*wu)[SL_THREADS / 64]) {
+    const int t = threadIdx.x;
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 k1 = __shfl_xor(a.k1, o, 64), k2 = __shfl_xor(a.k2, o, 64);
+        const unsigned s = __shfl_xor(a.s, o, 64), lo = __shfl_xor(a.lo, o, 64), hi = __shfl_xor(a.hi, o, 64);
+        pick_merge(a, k1, k2, s, lo, hi);
+    }
+    if ((t & 63) == 0) {
+        wk[0][t >> 6] = a.k1;
+        wk[1][t >> 6] = a.k2;
+        wu[0][t >> 6] = a.s;
+        wu[1][t >> 6] = a.lo;
+        wu[2][t >> 6] = a.hi;
+    }
+    __syncthreads();
+    if (t == 0)
+        for (int q = 1; q < SL_THREADS / 64; ++q) pick_merge(a, wk[0][q], wk[1][q], wu[0][q], wu[1][q], wu[2][q]);
+}
+
+__global__ __launch_bounds__(SL_THREADS) void k_sweepw_select(const u64* __restrict__ profw,
+                                                              const u64* __restrict__ prefix, unsigned n, u64 total,
+                                                              u64 max_part, u64* __restrict__ part) {
+    __shared__ u64 wk[2][SL_THREADS / 64];
+    __shared__ unsigned wu[3][SL_THREADS / 64];
+    Pick a{0ull, 0ull, SL_NONE, SL_NONE, 0u};
+    const u64 step = u64(gridDim.x) * SL_THREADS;
+    for (u64 s = 1ull + u64(blockIdx.x) * SL_THREADS + threadIdx.x; s < u64(n); s += step) {
+        const u64 p = prefix[s], c = profw[s];
+        const u64 twice = 2ull * p, d = twice >= total ? twice - total : total - twice;
+        // (p <= W for the prefix a scan left; a greater one would wrap to a side above L_max)
+        const bool feasible = p <= max_part && total - p <= max_part;
+        pick_merge(a, feasible ? c : (1ull << 63) | d, feasible ? d : c, unsigned(s), feasible ? unsigned(s) : SL_NONE,
+                   feasible ? unsigned(s) : 0u);
+    }
+    pick_block(a, wk, wu);
+    if (threadIdx.x == 0) {
+        u64* out = part + size_t(SL_WORDS) * blockIdx.x;
+        out[0] = a.k1;
+        out[1] = a.k2;
+        out[2] = a.s;
+        out[3] = a.lo;
+        out[4] = a.hi;
+    }
+}
+
+// rec = {s*, feasible, s_lo, s_hi, profile_w[s*], profile[s*], profile_w[n / 2],
+//        the nets with lo < hi, P[s*], P[n]}
+__global__ __launch_bounds__(SL_THREADS) void k_sweepw_finish(const u64* __restrict__ part, int nparts,
+                                                              const u64* __restrict__ profw,
+                                                              const u64* __restrict__ prefix,
+                                                              const unsigned* __restrict__ profile, unsigned n,
+                                                              const unsigned* __restrict__ span_part, int nspan,
+                                                              long long* __restrict__ rec) {
+    __shared__ u64 wk[2][SL_THREADS / 64];
+    __shared__ unsigned wu[3][SL_THREADS / 64];
+    __shared__ u64 sp[SL_THREADS / 64];
+    const int t = threadIdx.x;
+    Pick a{0ull, 0ull, SL_NONE, SL_NONE, 0u};
+    for (int b = t; b < nparts; b += SL_THREADS) {
+        const u64* in = part + size_t(SL_WORDS) * b;
+        pick_merge(a, in[0], in[1], unsigned(in[2]), unsigned(in[3]), unsigned(in[4]));
+    }
+    u64 spans = span_share(span_part, nspan, t);
+    for (int o = 32; o > 0; o >>= 1) spans += __shfl_xor(spans, o, 64);
+    if ((t & 63) == 0) sp[t >> 6] = spans;
+    pick_block(a, wk, wu);  // (its barrier also publishes sp)
+    if (t == 0) {
+        const bool any = a.s != SL_NONE, feasible = a.lo != SL_NONE;
+        rec[0] = any ? (long long)a.s : -1ll;
+        rec[1] = feasible ? 1ll : 0ll;
+        rec[2] = feasible ? (long long)a.lo : 0ll;
+        rec[3] = feasible ? (long long)a.hi : 0ll;
+        rec[4] = any ? (long long)profw[a.s] : 0ll;
+        rec[5] = any ? (long long)profile[a.s] : 0ll;
+        rec[6] = (long long)profw[n / 2u];
+        rec[7] = (long long)(sp[0] + sp[1] + sp[2] + sp[3]);
+        rec[8] = any ? (long long)prefix[a.s] : 0ll;
+        rec[9] = (long long)prefix[n];
+    }
+}
+static_assert(SWEEPW_REC == 10, "the record k_sweepw_finish writes");
+
+// ---------------------------------------------------------------------------
 // launchers
 int sweep_tiles(int n) { return (n + SWEEP_TILE - 1) / SWEEP_TILE; }
 
-size_t sweep_scan_tmp_words(long long count) { return size_t((count + SC_BLOCK - 1) / SC_BLOCK) + 1; }
+size_t sweep_scan_tmp_words(long long count) { return size_t((count + SWEEP_SCAN_BLOCK - 1) / SWEEP_SCAN_BLOCK) + 1; }
 
-void sweep_scan(hipStream_t s, unsigned* data, long long count, bool inclusive, unsigned* tmp) {
+template <class T>
+void sweep_scan(hipStream_t s, T* data, long long count, bool inclusive, T* tmp) {
+    constexpr bool WIDE = std::is_same_v<T, u64>;  // no caller wants the exclusive 64-bit scan: none is compiled
+    if (WIDE && !inclusive) fail(EK_EINVAL, "sweep_scan: the 64-bit scan is inclusive only");
     if (count <= 0) return;
-    const int nb = int((count + SC_BLOCK - 1) / SC_BLOCK);
-    hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(SC_THREADS), 0, s, data, count, tmp);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SC_THREADS), 0, s, tmp, nb);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(SC_THREADS), 0, s, data, count, tmp, inclusive ? 1 : 0);
+    const int nb = int((count + SWEEP_SCAN_BLOCK - 1) / SWEEP_SCAN_BLOCK);
+    hipLaunchKernelGGL(k_scan_sums<T>, dim3(nb), dim3(SC_THREADS), 0, s, data, count, tmp);
+    hipLaunchKernelGGL(k_scan_top<T>, dim3(1), dim3(SC_THREADS), 0, s, tmp, nb);
+    if constexpr (WIDE) {
+        hipLaunchKernelGGL((k_scan_apply<T, Inclusive>), dim3(nb), dim3(SC_THREADS), 0, s, data, count, tmp, Inclusive{});
+    } else {
+        hipLaunchKernelGGL((k_scan_apply<T, int>), dim3(nb), dim3(SC_THREADS), 0, s, data, count, tmp, inclusive ? 1 : 0);
+    }
 }
+template void sweep_scan(hipStream_t, unsigned*, long long, bool, unsigned*);
+template void sweep_scan(hipStream_t, u64*, long long, bool, u64*);
 
 void sweep_keys(hipStream_t s, const double* v, int n, u64* keys, int32_t* ids, unsigned* ghist) {
     hipLaunchKernelGGL(k_sweep_keys, dim3(sweep_tiles(n)), dim3(SW_THREADS), 0, s, v, n, keys, ids, ghist);
@@ -429,10 +626,19 @@ void sweep_pos(hipStream_t s, const int32_t* order, int n, int32_t* pos) {
 int sweep_span_blocks(int64_t nets) { return int((nets + SP_THREADS - 1) / SP_THREADS); }
 
 void sweep_spans(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* pos, int n,
-                 unsigned* diff, unsigned* span_part) {
+                 unsigned* diff, unsigned* span_part, const int32_t* cw, u64* diffw) {
     if (nets <= 0) return;
-    hipLaunchKernelGGL(k_sweep_spans, dim3(unsigned(sweep_span_blocks(nets))), dim3(SP_THREADS), 0, s, (long long)nets,
-                       net_ptr, pins, pos, n, diff, span_part);
+    const dim3 grid(unsigned(sweep_span_blocks(nets)));
+    if (diffw)
+        hipLaunchKernelGGL(k_sweep_spans<NetWeights>, grid, dim3(SP_THREADS), 0, s, (long long)nets, net_ptr, pins, pos, n,
+                           diff, span_part, NetWeights{cw, diffw});
+    else
+        hipLaunchKernelGGL(k_sweep_spans<NoWeights>, grid, dim3(SP_THREADS), 0, s, (long long)nets, net_ptr, pins, pos, n,
+                           diff, span_part, NoWeights{});
+}
+
+void sweepw_gather(hipStream_t s, const int32_t* order, const int32_t* w, int n, u64* pw) {
+    hipLaunchKernelGGL(k_sweepw_gather, dim3((n + SP_THREADS - 1) / SP_THREADS), dim3(SP_THREADS), 0, s, order, w, n, pw);
 }
 
 int sweep_select_blocks(int64_t window) {
@@ -445,6 +651,19 @@ void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, i
     hipLaunchKernelGGL(k_sweep_select, dim3(nb), dim3(SL_THREADS), 0, s, profile, unsigned(n), unsigned(s_lo),
                        unsigned(s_hi), objective, part);
     hipLaunchKernelGGL(k_sweep_finish, dim3(1), dim3(SL_THREADS), 0, s, part, nb, profile, unsigned(n), objective,
+                       span_part, nspan, rec);
+}
+
+int sweepw_select_blocks(int n) {
+    return int(std::max<int64_t>(1, std::min<int64_t>(SWEEP_SELECT_MAX_BLOCKS, (int64_t(n) - 1 + SL_THREADS - 1) / SL_THREADS)));
+}
+
+void sweepw_select(hipStream_t s, const u64* profw, const u64* prefix, const unsigned* profile, int n, u64 total,
+                   u64 max_part, u64* part, const unsigned* span_part, int nspan, long long* rec) {
+    const int nb = sweepw_select_blocks(n);
+    hipLaunchKernelGGL(k_sweepw_select, dim3(nb), dim3(SL_THREADS), 0, s, profw, prefix, unsigned(n), total, max_part,
+                       part);
+    hipLaunchKernelGGL(k_sweepw_finish, dim3(1), dim3(SL_THREADS), 0, s, part, nb, profw, prefix, profile, unsigned(n),
                        span_part, nspan, rec);
 }
 

@@ -33,13 +33,6 @@ void chk(int rc) {
     if (rc != EK_OK) throw ek::Error{rc};  // ek_last_error() already holds the message
 }
 
-// the radix order of the device select (ord_key, kernels_kl.hip)
-inline uint64_t ord_key(double v) {
-    uint64_t u;
-    std::memcpy(&u, &v, 8);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 void plan(int64_t n, int32_t k, int64_t* sizes) {
     if (k == 1) {
         sizes[0] = n;
@@ -227,7 +220,7 @@ int ek_rank_split(int64_t n, const double* v, int64_t n1, uint8_t* bits_out) {
     // the key at rank n1 - 1, the keys below it, then the equal keys in id
     // order: the device kernels' steps (kernels_kway.hip)
     std::vector<uint64_t> key(static_cast<size_t>(n));
-    for (int64_t i = 0; i < n; ++i) key[size_t(i)] = ord_key(v[i]);
+    for (int64_t i = 0; i < n; ++i) key[size_t(i)] = ek::ord_key(v[i]);
     std::vector<uint64_t> tmp(key);
     std::nth_element(tmp.begin(), tmp.begin() + (n1 - 1), tmp.end());
     const uint64_t K = tmp[size_t(n1 - 1)];

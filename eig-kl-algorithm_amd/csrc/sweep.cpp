@@ -1,16 +1,21 @@
-// Sweep cut of a Fiedler vector under a balance tolerance: the host pieces.
+// The sweep cuts of a Fiedler vector, by net count under a balance tolerance
+// and by net weight under a node-weight bound: the host pieces.
 //
-// ek_sweep_cut_host is the checker of the device path (ek_sweep_cut,
-// ctx_sweep.cpp + kernels_sweep.hip).  It is single-threaded and written from
-// the rule (eigkl.h), not from the kernels: a std::sort on
-// (key, id) where the device runs a radix sort, one loop over each net's pins,
-// a difference array and one linear pass with 128-bit products where the
-// device reduces with two 64-bit words.  The two share only the argument
-// checks and the window (sweep_check, sweep_window).
+// ek_sweep_cut_host and ek_sweep_cut_w_host are the checkers of the device
+// paths (ek_sweep_cut, ek_sweep_cut_w; ctx_sweep.cpp + kernels_sweep.hip).
+// They are single-threaded and written from the rules (eigkl.h, DESIGN.md §10
+// and §13), not from the kernels: a std::sort on (key, id) where the device
+// runs a radix sort, one loop over each net's pins, difference arrays and
+// running sums where the device scans, and linear passes for the choice: with
+// 128-bit products where the count sweep's kernels reduce with two 64-bit
+// words, and one pass for the window and one for the choice where the weighted
+// sweep's run one keyed reduction.  Host and device share only the argument
+// checks, the count sweep's window and the weighted sweep's L_max (sweep_check,
+// sweep_window, sweepw_check); the two checkers share the order and a net's
+// span, which the two rules state in the same words.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstring>
 #include <memory>
 #include <string>
 #include <utility>
@@ -26,11 +31,32 @@ void chk(int rc) {
     if (rc != EK_OK) throw ek::Error{rc};
 }
 
-// the radix order of the device select (ord_key, kway.cpp)
-inline uint64_t ord_key(double v) {
-    uint64_t u;
-    std::memcpy(&u, &v, 8);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+constexpr int64_t W_LIMIT = int64_t(1) << 62;  // of W and of the sum of all c(e)
+
+using Keyed = std::vector<std::pair<uint64_t, int32_t>>;
+
+// the order: keyed ascending by (ord(v[i]), i), the keys compared, never the
+// doubles; pos[keyed[r].second] = r
+void order_by_key(const double* v, int64_t n, Keyed& keyed, std::vector<int32_t>& pos) {
+    keyed.resize(static_cast<size_t>(n));
+    for (int64_t i = 0; i < n; ++i) keyed[size_t(i)] = {ek::ord_key(v[i]), int32_t(i)};
+    std::sort(keyed.begin(), keyed.end());
+    pos.resize(static_cast<size_t>(n));
+    for (int64_t rnk = 0; rnk < n; ++rnk) pos[size_t(keyed[size_t(rnk)].second)] = int32_t(rnk);
+}
+
+// the least and the greatest rank of net e's pins; false: the net has fewer
+// than two pins or all of them at one rank, and is cut by no split
+bool net_span(const ek_hgr* h, int64_t e, const std::vector<int32_t>& pos, int32_t& lo, int32_t& hi) {
+    const int64_t p0 = h->net_ptr[size_t(e)], p1 = h->net_ptr[size_t(e) + 1];
+    if (p1 - p0 < 2) return false;
+    lo = INT32_MAX, hi = -1;
+    for (int64_t p = p0; p < p1; ++p) {
+        const int32_t x = pos[size_t(h->pins[size_t(p)])];
+        lo = std::min(lo, x);
+        hi = std::max(hi, x);
+    }
+    return lo != hi;
 }
 }  // namespace
 
@@ -55,6 +81,34 @@ void sweep_window(int64_t n, double imbalance, ek_sweep_result& r) {
     r.max_part = refine_max_part(n, 2, imbalance);
     r.s_lo = std::max<int64_t>(1, n - r.max_part);
     r.s_hi = std::min<int64_t>(n - 1, r.max_part);
+}
+
+ek_sweep_opts sweepw_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts,
+                           ek_sweep_w_result& r) {
+    const ek_sweep_opts o = sweep_check(who, h, v, opts);
+    if (o.objective != 0)
+        fail(EK_EINVAL, "%s: objective %d (the weighted sweep has the minimum cut only)", who, int(o.objective));
+    const int64_t n = h->nodes;
+    if (!h->node_w.empty() && int64_t(h->node_w.size()) != n)
+        fail(EK_EINVAL, "%s: %lld node weights for %lld nodes", who, (long long)h->node_w.size(), (long long)n);
+    if (!h->net_w.empty() && int64_t(h->net_w.size()) != h->nets)
+        fail(EK_EINVAL, "%s: %lld net weights for %lld nets", who, (long long)h->net_w.size(), (long long)h->nets);
+    int64_t total = h->node_w.empty() ? n : 0, csum = h->net_w.empty() ? h->nets : 0;
+    for (const int32_t w : h->node_w) {
+        if (w < 0) fail(EK_EINVAL, "%s: node weight %d", who, w);
+        total += w;
+    }
+    for (const int32_t c : h->net_w) {
+        if (c < 1) fail(EK_EINVAL, "%s: net weight %d", who, c);
+        csum += c;
+    }
+    // (int32 weights over fewer than 2^31 nodes and nets stay below both limits; the rule states them all the same)
+    if (total > W_LIMIT || csum > W_LIMIT) fail(EK_EINVAL, "%s: total weight above 2^62", who);
+    r = ek_sweep_w_result{};
+    r.n = n;
+    r.total_weight = total;
+    r.max_part = refine_max_part(total, 2, o.imbalance);
+    return o;
 }
 
 // `gKL2 <in> -EIG --sweep EPS [--sweep-ratio]` (cli.cpp refers to it weakly):
@@ -93,6 +147,59 @@ int sweep_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lan
     EK_CATCH
 }
 
+// `gKL2 <in> -EIG --sweep EPS --sweep-weighted --fm EPS --weighted [--no-kl]`
+// (cli.cpp refers to it weakly): the hMETIS reading of the file, the Laplacian
+// on the device, Lanczos, then the weighted sweep split.  With KL: the KL
+// graph and nets, the split into the context, the KL loop and the sides of its
+// best prefix.  Without: the sides ek_rank_split(v, n1) as they are (KL swaps
+// pairs and ignores weights, so it can leave the bound the sweep kept).  Then
+// ek_fm_refine_w and results/<base>.part.2.
+int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, double sweep_eps, int no_kl,
+                        double imbalance, int max_passes, int stall, ek_sweep_w_result* sr, ek_kl_result* kr,
+                        ek_fm_w_result* fr);
+int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, double sweep_eps, int no_kl,
+                        double imbalance, int max_passes, int stall, ek_sweep_w_result* sr, ek_kl_result* kr,
+                        ek_fm_w_result* fr) {
+    EK_TRY
+    if (!ctx || !path || !so || !sr || !kr || !fr) fail(EK_EINVAL, "sweepw: null argument");
+    ek_fm_opts fo;
+    ek_fm_default_opts(&fo);
+    fo.imbalance = imbalance;
+    fo.max_passes = max_passes;
+    if (stall >= 0) fo.stall = stall;  // (< 0: the default)
+    ek_hgr* h = nullptr;
+    chk(ek_hgr_read_weighted(path, &h));
+    std::unique_ptr<ek_hgr, void (*)(ek_hgr*)> hg(h, ek_hgr_free);
+    if (h->nodes < 2) fail(EK_EINVAL, "sweepw: %lld nodes", (long long)h->nodes);
+    ek_sweep_opts wo;
+    ek_sweep_default_opts(&wo);
+    wo.imbalance = sweep_eps;
+    chk(spmv_setup_hgr(ctx, *h, nullptr));
+    double lam = 0.0;
+    ek_lanczos_stats ls{};
+    std::vector<uint8_t> sides(static_cast<size_t>(h->nodes));
+    *kr = ek_kl_result{};
+    if (no_kl) {
+        std::vector<double> v(static_cast<size_t>(h->nodes));
+        chk(ek_lanczos_fiedler(ctx, &so->lanczos, &lam, v.data(), &ls));
+        chk(ek_sweep_cut_w(ctx, h, v.data(), &wo, nullptr, nullptr, nullptr, sr));
+        chk(ek_rank_split(h->nodes, v.data(), sr->n1, sides.data()));
+    } else {
+        chk(ek_lanczos_fiedler(ctx, &so->lanczos, &lam, nullptr, &ls));
+        const std::function<ek_ctx*()> get = [ctx] { return ctx; };
+        ThreadStatus ts = kl_graph_host(&get, h, kl_graph_threads(false));
+        if (ts.code != EK_OK) fail(ts.code, "KL graph setup: %s", ts.msg.c_str());
+        chk(ek_kl_set_partition_fiedler_sweep_w(ctx, h, &wo, sr));
+        chk(ek_kl_run(ctx, so->limit, nullptr, 0, kr));
+        chk(ek_kl_sides(ctx, 1, sides.data()));
+    }
+    chk(ek_fm_refine_w(ctx, h, &fo, sides.data(), nullptr, 0, nullptr, 0, fr));
+    std::vector<int32_t> part(sides.begin(), sides.end());
+    write_part_file(path, nullptr, 2, h->nodes, part.data());
+    return EK_OK;
+    EK_CATCH
+}
+
 }  // namespace ek
 
 extern "C" {
@@ -112,28 +219,19 @@ int ek_sweep_cut_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opt
     ek_sweep_result r{};
     ek::sweep_window(n, o.imbalance, r);
 
-    // 1. order: ascending (ord(v[i]), i); the keys are compared, never the doubles
+    // 1. order
     auto t = clk::now();
-    std::vector<std::pair<uint64_t, int32_t>> keyed(static_cast<size_t>(n));
-    for (int64_t i = 0; i < n; ++i) keyed[size_t(i)] = {ord_key(v[i]), int32_t(i)};
-    std::sort(keyed.begin(), keyed.end());
-    std::vector<int32_t> pos(static_cast<size_t>(n));
-    for (int64_t rnk = 0; rnk < n; ++rnk) pos[size_t(keyed[size_t(rnk)].second)] = int32_t(rnk);
+    Keyed keyed;
+    std::vector<int32_t> pos;
+    order_by_key(v, n, keyed, pos);
     r.t_sort = since(t);
 
     // 2. profile: +1 at lo + 1, -1 at hi + 1, an inclusive prefix sum
     t = clk::now();
     std::vector<int64_t> prof(static_cast<size_t>(n) + 1, 0);
     for (int64_t e = 0; e < h->nets; ++e) {
-        const int64_t p0 = h->net_ptr[size_t(e)], p1 = h->net_ptr[size_t(e) + 1];
-        if (p1 - p0 < 2) continue;
-        int32_t lo = INT32_MAX, hi = -1;
-        for (int64_t p = p0; p < p1; ++p) {
-            const int32_t x = pos[size_t(h->pins[size_t(p)])];
-            lo = std::min(lo, x);
-            hi = std::max(hi, x);
-        }
-        if (lo == hi) continue;
+        int32_t lo = 0, hi = 0;
+        if (!net_span(h, e, pos, lo, hi)) continue;
         ++r.spanning_nets;
         ++prof[size_t(lo) + 1];
         --prof[size_t(hi) + 1];
@@ -170,6 +268,85 @@ int ek_sweep_cut_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opt
         for (int64_t rnk = 0; rnk < n; ++rnk) order_out[rnk] = keyed[size_t(rnk)].second;
     if (profile_out)
         for (int64_t s = 0; s <= n; ++s) profile_out[s] = int32_t(prof[size_t(s)]);
+    if (result) *result = r;
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_sweep_cut_w_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opts, int32_t* order_out,
+                        int64_t* profile_out, int64_t* prefix_out, ek_sweep_w_result* result) {
+    EK_TRY
+    ek_sweep_w_result r{};
+    ek::sweepw_check("ek_sweep_cut_w_host", h, v, opts, r);
+    const int64_t n = h->nodes, W = r.total_weight, lmax = r.max_part;
+
+    // 1. order
+    auto t = clk::now();
+    Keyed keyed;
+    std::vector<int32_t> pos;
+    order_by_key(v, n, keyed, pos);
+    r.t_sort = since(t);
+
+    // 2. the weighted and the count profile: +c / +1 at lo + 1, -c / -1 at hi + 1, inclusive prefix sums
+    // 3. P[s]: the running sum of w(order[r])
+    t = clk::now();
+    std::vector<int64_t> profw(static_cast<size_t>(n) + 1, 0), prof(static_cast<size_t>(n) + 1, 0),
+        prefix(static_cast<size_t>(n) + 1, 0);
+    for (int64_t e = 0; e < h->nets; ++e) {
+        int32_t lo = 0, hi = 0;
+        if (!net_span(h, e, pos, lo, hi)) continue;
+        const int64_t c = h->net_w.empty() ? 1 : h->net_w[size_t(e)];
+        ++r.spanning_nets;
+        profw[size_t(lo) + 1] += c;
+        profw[size_t(hi) + 1] -= c;
+        ++prof[size_t(lo) + 1];
+        --prof[size_t(hi) + 1];
+    }
+    for (int64_t s = 1; s <= n; ++s) {
+        profw[size_t(s)] += profw[size_t(s) - 1];
+        prof[size_t(s)] += prof[size_t(s) - 1];
+        const int32_t node = keyed[size_t(s) - 1].second;
+        prefix[size_t(s)] = prefix[size_t(s) - 1] + (h->node_w.empty() ? 1 : h->node_w[size_t(node)]);
+    }
+    r.t_profile = since(t);
+
+    // 4. the window; 5. the choice.  |2 P - W| <= W <= 2^62 and 2 P <= 2^63: unsigned
+    t = clk::now();
+    auto dist = [&](int64_t s) {
+        const uint64_t twice = 2 * uint64_t(prefix[size_t(s)]), w = uint64_t(W);
+        return twice >= w ? twice - w : w - twice;
+    };
+    auto is_feasible = [&](int64_t s) { return prefix[size_t(s)] <= lmax && W - prefix[size_t(s)] <= lmax; };
+    for (int64_t s = 1; s <= n - 1; ++s)
+        if (is_feasible(s)) {
+            if (!r.feasible) r.s_lo = s;
+            r.s_hi = s;
+            r.feasible = 1;
+        }
+    int64_t best = r.feasible ? r.s_lo : 1;
+    if (r.feasible) {
+        for (int64_t s = r.s_lo + 1; s <= r.s_hi; ++s) {  // least (profile_w, |2P - W|, s): a later s only when strictly less
+            if (profw[size_t(s)] != profw[size_t(best)] ? profw[size_t(s)] < profw[size_t(best)] : dist(s) < dist(best))
+                best = s;
+        }
+    } else {
+        for (int64_t s = 2; s <= n - 1; ++s) {  // least (|2P - W|, profile_w, s)
+            if (dist(s) != dist(best) ? dist(s) < dist(best) : profw[size_t(s)] < profw[size_t(best)]) best = s;
+        }
+    }
+    r.n1 = best;
+    r.n0 = n - best;
+    r.w1 = prefix[size_t(best)];
+    r.w0 = W - r.w1;
+    r.cut = profw[size_t(best)];
+    r.cut_nets = prof[size_t(best)];
+    r.cut_half = profw[size_t(n / 2)];
+    r.t_select = since(t);
+
+    if (order_out)
+        for (int64_t rnk = 0; rnk < n; ++rnk) order_out[rnk] = keyed[size_t(rnk)].second;
+    if (profile_out) std::copy(profw.begin(), profw.end(), profile_out);
+    if (prefix_out) std::copy(prefix.begin(), prefix.end(), prefix_out);
     if (result) *result = r;
     return EK_OK;
     EK_CATCH

@@ -12,7 +12,7 @@ EPSILONS = (0.0, 0.03, 0.5, 10.0)
 INTS = ("n", "n0", "n1", "s_lo", "s_hi", "max_part", "cut", "cut_mid", "spanning_nets")
 TILE = 2048  # keys per workgroup of a sort pass (SWEEP_TILE, ek_internal.hpp)
 # 10 tiles: the (digit, tile) table has 2,560 words, and its scan takes 2,048
-# words a workgroup, so the scan spans two workgroups
+# words a workgroup (SWEEP_SCAN_BLOCK, ek_internal.hpp), so the scan spans two workgroups
 N_TABLE_SCAN_SPANS_WORKGROUPS = 20000
 
 

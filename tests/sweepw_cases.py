@@ -14,10 +14,10 @@ EPSILONS = (0.0, 0.03, 0.25)
 INTS = ("n", "n0", "n1", "s_lo", "s_hi", "feasible", "total_weight", "max_part", "w0", "w1", "cut", "cut_nets",
         "cut_half", "spanning_nets")
 INT32_MAX = 2 ** 31 - 1
-SCAN_BLOCK = 2048  # 64-bit words per workgroup of the scan (SWEEPW_SCAN_BLOCK, ek_internal.hpp)
-SCAN_TOP = 256  # block sums per step of the top scan's one workgroup (SWEEPW_SCAN_TOP, ek_internal.hpp)
-# k_scan64_top walks the block sums SCAN_TOP at a step and carries the running
-# total between steps.  The scans run over n + 1 words, so up to n + 1 =
+SCAN_BLOCK = 2048  # words per workgroup of a scan, of either width (SWEEP_SCAN_BLOCK, ek_internal.hpp)
+SCAN_TOP = 256  # block sums per step of the top scan's one workgroup (SC_THREADS, kernels_sweep.hip)
+# k_scan_top, for both word widths, walks the block sums SCAN_TOP at a step and
+# carries the running total between steps.  The scans run over n + 1 words, so up to n + 1 =
 # SCAN_TOP * SCAN_BLOCK = 524,288 words there is one step and the carry is
 # never used; n = 524,288 (524,289 words, 257 block sums) is the smallest n
 # whose scan takes the second step.

@@ -42,7 +42,7 @@ def same_as_host(ek, ctx, h, v, eps):
 
 @pytest.mark.parametrize("name", wc.names())
 def test_device_equals_host(ek, ctx, name):
-    """Among the cases: n + 1 = 2,047 | 2,048 | 2,049 words (n2046, n2047, n2048: the 64-bit scan's block edge), nets
+    """Among the cases: n + 1 = 2,047 | 2,048 | 2,049 words (n2046, n2047, n2048: the scans' block edge), nets
     of 8 | 9, 64 | 65 and n pins (metrics+all: thread / wave hand-over), 5,000 nets on one lo and one hi at weight
     2^31 - 1 (contended: carries into the high word), no feasible split (heavy_node)."""
     h, v, epsilons = wc.hypergraph(ek, name)
@@ -52,8 +52,9 @@ def test_device_equals_host(ek, ctx, name):
 
 
 def test_scan_of_block_sums_second_step(ek, ctx):
-    """n = 524,288: the scans run over n + 1 = 256 * 2,048 + 1 words, 257 block sums, and k_scan64_top takes 256 a
-    step, so this is the smallest n at which its second step, with the carry of the first, runs."""
+    """n = 524,288: the scans run over n + 1 = 256 * 2,048 + 1 words, 257 block sums, and k_scan_top takes 256 a
+    step, so this is the smallest n at which its second step, with the carry of the first, runs: in its 64-bit
+    instantiation (profile_w, P) and in its 32-bit one (the count profile)."""
     n, ptr, pins, node_w, net_w, v = wc.big_case()
     assert n == wc.N_TOP_SCAN_SECOND_STEP == 524288 and -(-(n + 1) // wc.SCAN_BLOCK) == wc.SCAN_TOP + 1
     h = ek.Hypergraph.from_pins(n, ptr, pins)
