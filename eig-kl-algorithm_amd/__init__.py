@@ -280,6 +280,8 @@ _sig("ek_kl_nets_setup", ctypes.c_int, _P, _I64, _P, _P)
 _sig("ek_kl_set_partition", ctypes.c_int, _P, _P, _I64, _P, _I64)
 _sig("ek_kl_set_partition_bits", ctypes.c_int, _P, _I64, _P)
 _sig("ek_kl_set_partition_fiedler", ctypes.c_int, _P, _P, _P, _P)
+_sig("ek_fiedler_set", ctypes.c_int, _P, _I64, _P)
+_sig("ek_kl_partition_copy", ctypes.c_int, _P, _P, _P, _P, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64))
 _sig("ek_kl_run", ctypes.c_int, _P, _I32, _P, _I64, ctypes.POINTER(KLResult))
 _sig("ek_kl_sides", ctypes.c_int, _P, _I32, _P)
 _sig("ek_cli_main", ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p))
@@ -995,6 +997,28 @@ class Context:
              "kl_set_partition_fiedler")
         self._n01 = (n0.value, n1.value)
         return med.value, n0.value, n1.value
+
+    def fiedler_set(self, v):
+        """Uploads v as this context's Fiedler vector, the state a successful lanczos_fiedler leaves for
+        kl_set_partition_fiedler and its rank / sweep kin (ek_fiedler_set).  None passes a null pointer."""
+        if v is None:
+            return _chk(_lib.ek_fiedler_set(self._c, 1, None), "fiedler_set")
+        v =np.ascontiguousarray(v, np.float64)
+        _chk(_lib.ek_fiedler_set(self._c, len(v), _p(v)), "fiedler_set")
+
+    def kl_partition_copy(self):
+        """What the last kl_set_partition* call left on the device (ek_kl_partition_copy): a dict of order0,
+        order1 (the lists' node ids), plist (position in its list, bit 31 on side 1), side, n0 and n1."""
+        n0, n1 = ctypes.c_int64(), ctypes.c_int64()
+        _chk(_lib.ek_kl_partition_copy(self._c, None, None, None, None, ctypes.byref(n0), ctypes.byref(n1)),
+             "kl_partition_copy")
+        n = n0.value + n1.value
+        out = {"order0": np.empty(n0.value, np.int32), "order1": np.empty(n1.value, np.int32),
+               "plist": np.empty(n, np.uint32), "side": np.empty(n, np.uint8)}
+        _chk(_lib.ek_kl_partition_copy(self._c, _p(out["order0"]), _p(out["order1"]), _p(out["plist"]),
+                                       _p(out["side"]), None, None), "kl_partition_copy")
+        out["n0"], out["n1"] = n0.value, n1.value
+        return out
 
     def kl_set_partition_fiedler_rank(self, n1):
         """kl_set_partition_fiedler with the rank split: side 1 gets the n1 nodes rank_split marks in the

@@ -6,7 +6,10 @@ using namespace ek::rt;
 
 Uploader::Uploader(ek_ctx* ctx, hipStream_t st, size_t total)
     : c(ctx), s(st), buf(st == ctx->kstream ? ctx->kup : ctx->up), cap(st == ctx->kstream ? ctx->kup_bytes : ctx->up_bytes) {
-    total = (total + 64) * 2;  // alignment slack
+    // alignment slack: every put starts on a 64-byte line, so up to eight of
+    // them fit whatever their sizes (a two-node partition's four puts hold 18
+    // bytes and end at offset 200)
+    total = total * 2 + 64 * 8;
     if (cap < total) {
         // the arena's previous user drained its stream before returning
         if (buf) HIPCHK(hipHostFree(buf));

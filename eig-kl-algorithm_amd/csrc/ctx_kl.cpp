@@ -186,12 +186,36 @@ int ek_kl_set_partition(ek_ctx* c, const int32_t* order0, int64_t n0, const int3
         plist[size_t(u)] = uint32_t(i) | 0x80000000u;
     }
     hipStream_t s = c->stream;
+    c->kl.part_ready = false;  // the lists are rewritten from here on
     Uploader up(c, s, size_t(n0) * 4 + size_t(n1) * 4 + size_t(n) + size_t(n) * 4);
     up.put(c->kl.order0, order0, size_t(n0));
     up.put(c->kl.order1, order1, size_t(n1));
     up.put(c->kl.side_init, side.data(), size_t(n));
     up.put(c->kl.plist, plist.data(), size_t(n));
     partition_on_device(c, n0, n1);
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_fiedler_set(ek_ctx* c, int64_t n, const double* v_host) {
+    EK_TRY
+    check_ctx(c);
+    if (c->nranks > 1) ek::fail(EK_ESTATE, "ek_fiedler_set: a multi-rank context (%d ranks); the splits run on one", c->nranks);
+    if (n < 1 || n > INT32_MAX - 1 || !v_host) ek::fail(EK_EINVAL, "ek_fiedler_set: bad argument");
+    {
+        // a NaN has no place in the select's order, and a solve never leaves one
+        std::atomic<bool> bad{false};
+        ek::parallel_for(n, [&](int64_t lo, int64_t hi) {
+            for (int64_t i = lo; i < hi; ++i)
+                if (v_host[i] != v_host[i]) bad = true;
+        });
+        if (bad) ek::fail(EK_EINVAL, "ek_fiedler_set: NaN in the vector");
+    }
+    hipStream_t s = c->stream;
+    c->fied_n = 0;  // as a solve does: no vector until this one is whole on the device
+    upload(c->fied, v_host, size_t(n), s);
+    HIPCHK(hipStreamSynchronize(s));
+    c->fied_n = n;
     return EK_OK;
     EK_CATCH
 }
@@ -221,6 +245,7 @@ int ek_kl_set_partition_fiedler(ek_ctx* c, double* median_out, int64_t* n0_out, 
     HIPCHK(hipStreamSynchronize(s));
     const double mid[2] = {ek::dev::key_value(kk[0]), ek::dev::key_value(kk[1])};
     const double med = n % 2 == 0 ? (mid[0] + mid[1]) / 2.0 : mid[0];
+    c->kl.part_ready = false;  // the lists are rewritten from here on: a failure must not leave the old partition's flag
     c->kl.order0.ensure(size_t(n) * 4);
     c->kl.order1.ensure(size_t(n) * 4);
     c->kl.side_init.ensure(size_t(n));
@@ -302,6 +327,7 @@ int ek_kl_set_partition_fiedler_rank(ek_ctx* c, int64_t n1, int64_t* n0_out, int
     if (n > INT32_MAX - 1) ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler_rank: %lld nodes", (long long)n);
     if (n1 < 1 || n1 >= n)
         ek::fail(EK_EINVAL, "ek_kl_set_partition_fiedler_rank: n1 = %lld outside [1, %lld)", (long long)n1, (long long)n);
+    c->kl.part_ready = false;  // as in ek_kl_set_partition_fiedler
     c->kl.order0.ensure(size_t(n) * 4);
     c->kl.order1.ensure(size_t(n) * 4);
     c->kl.side_init.ensure(size_t(n));
@@ -327,6 +353,24 @@ int ek_kl_set_partition_bits(ek_ctx* c, int64_t n, const uint8_t* bits) {
         o[bits[i]].push_back(int32_t(i));
     }
     return ek_kl_set_partition(c, o[0].data(), int64_t(o[0].size()), o[1].data(), int64_t(o[1].size()));
+    EK_CATCH
+}
+
+int ek_kl_partition_copy(ek_ctx* c, int32_t* order0_out, int32_t* order1_out, uint32_t* plist_out, uint8_t* side_out,
+                         int64_t* n0_out, int64_t* n1_out) {
+    EK_TRY
+    check_ctx(c);
+    if (!c->kl.graph_ready || !c->kl.part_ready) ek::fail(EK_ESTATE, "ek_kl_partition_copy: no partition is set");
+    hipStream_t s = c->stream;
+    const size_t n = size_t(c->kl.n), n0 = size_t(c->kl.n0), n1 = size_t(c->kl.n1);
+    if (order0_out && n0) HIPCHK(hipMemcpyAsync(order0_out, c->kl.order0.p, n0 * 4, hipMemcpyDeviceToHost, s));
+    if (order1_out && n1) HIPCHK(hipMemcpyAsync(order1_out, c->kl.order1.p, n1 * 4, hipMemcpyDeviceToHost, s));
+    if (plist_out) HIPCHK(hipMemcpyAsync(plist_out, c->kl.plist.p, n * 4, hipMemcpyDeviceToHost, s));
+    if (side_out) HIPCHK(hipMemcpyAsync(side_out, c->kl.side_init.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n0_out) *n0_out = c->kl.n0;
+    if (n1_out) *n1_out = c->kl.n1;
+    return EK_OK;
     EK_CATCH
 }
 

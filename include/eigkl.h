@@ -393,6 +393,22 @@ int ek_kl_set_partition_bits(ek_ctx* ctx, int64_t n, const uint8_t* bits);
  * give on the host (cEIG.cpp:204-209 median, cKL.cpp:155-174 lists), without
  * the vector's round trip.  median_out, n0_out, n1_out may be null. */
 int ek_kl_set_partition_fiedler(ek_ctx* ctx, double* median_out, int64_t* n0_out, int64_t* n1_out);
+/* Uploads v_host (n doubles) as the context's Fiedler vector: exactly the
+ * state a successful ek_lanczos_fiedler leaves for ek_kl_set_partition_fiedler
+ * and its _rank / _sweep kin.  The test seam of the device splits: it drives
+ * them with a chosen vector.  EK_EINVAL for n < 1, n > INT32_MAX - 1, a null
+ * pointer or any NaN in v_host (a NaN has no place in the select's order, and
+ * a solve never leaves one; infinities and signed zeros are ordered and
+ * accepted).  EK_ESTATE on a multi-rank context.  No reference counterpart. */
+int ek_fiedler_set(ek_ctx* ctx, int64_t n, const double* v_host);
+/* Copies back what the last ek_kl_set_partition* call left on the device: the
+ * remain[] lists (order0: n0 node ids, order1: n1), plist (node i's position
+ * in its list, bit 31 set on side 1) and the initial sides (n bytes).  The
+ * swap loop never rewrites them, so a later ek_kl_run changes nothing here.
+ * Any pointer may be null.  EK_ESTATE when no partition is set.
+ * No reference counterpart. */
+int ek_kl_partition_copy(ek_ctx* ctx, int32_t* order0_out /* n0 */, int32_t* order1_out /* n1 */,
+                         uint32_t* plist_out /* n */, uint8_t* side_out /* n */, int64_t* n0_out, int64_t* n1_out);
 /* Run the swap loop to termination on the device (one persistent
  * workgroup; no host round trip per iteration).  limit < 0: floor(log2 n)+5
  * (cKL.cpp:303).  log_out may be NULL. */
