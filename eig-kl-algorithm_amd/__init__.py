@@ -236,6 +236,8 @@ _sig("ek_hgr_free", None, _P)
 _sig("ek_laplacian_build", ctypes.c_int, _P, ctypes.POINTER(_P))
 _sig("ek_kl_graph_build", ctypes.c_int, _P, ctypes.POINTER(_P))
 _sig("ek_laplacian_build_rows", ctypes.c_int, _P, _I64, _I64, ctypes.POINTER(_P))
+_sig("ek_laplacian_build_w", ctypes.c_int, _P, ctypes.POINTER(_P))
+_sig("ek_laplacian_build_rows_w", ctypes.c_int, _P, _I64, _I64, ctypes.POINTER(_P))
 _sig("ek_synchronize", ctypes.c_int, _P)
 _sig("ek_csr_dims", ctypes.c_int, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32))
 _sig("ek_csr_copy", ctypes.c_int, _P, _P, _P, _P, _P)
@@ -258,6 +260,7 @@ _sig("ek_solve_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(SolveOpt
 _sig("ek_spmv_setup", ctypes.c_int, _P, _I64, _I64, _I64, _P, _P, _P)
 _sig("ek_spmv", ctypes.c_int, _P, _P, _P, _P)
 _sig("ek_spmv_setup_pins", ctypes.c_int, _P, _I64, _I64, _P, _P, ctypes.POINTER(ctypes.c_int32))
+_sig("ek_spmv_setup_pins_w", ctypes.c_int, _P, _I64, _I64, _P, _P, _P, ctypes.POINTER(ctypes.c_int32))
 _sig("ek_spmv_host", ctypes.c_int, _P, _P, _P)
 _sig("ek_spmv_bytes", _I64, _P)
 _sig("ek_spmv_dims", ctypes.c_int, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64))
@@ -330,6 +333,10 @@ _sig("ek_ml_default_opts", None, ctypes.POINTER(MlOpts))
 _sig("ek_multilevel_bipartition", ctypes.c_int, _P, _P, ctypes.POINTER(MlOpts), _P, ctypes.POINTER(MlResult))
 _sig("ek_multilevel_bipartition_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(MlOpts), ctypes.c_char_p, _P,
      ctypes.POINTER(MlResult))
+_sig("ek_multilevel_bipartition_ex", ctypes.c_int, _P, _P, ctypes.POINTER(MlOpts), _I32, _P, ctypes.POINTER(MlResult))
+_sig("ek_multilevel_bipartition_file_ex", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(MlOpts), ctypes.c_char_p,
+     _I32, _P, ctypes.POINTER(MlResult))
+ML_WEIGHTED_LAPLACIAN = 1  # eigkl.h EK_ML_WEIGHTED_LAPLACIAN
 
 lib = _lib
 
@@ -498,16 +505,20 @@ class Hypergraph:
         _chk(_lib.ek_hgr_contract(self._h, _p(cluster), int(n_coarse), ctypes.byref(c)), "contract")
         return Hypergraph(c)
 
-    def laplacian(self):
-        """fp64 clique Laplacian (cEIG.cpp:86-133)."""
+    def laplacian(self, weighted=False):
+        """fp64 clique Laplacian (cEIG.cpp:86-133).  weighted: -(2 c(e) / |e|) per pin pair, c(e) the net weights
+        (ek_laplacian_build_w); without net weights the same arrays."""
         c = _P()
-        _chk(_lib.ek_laplacian_build(self._h, ctypes.byref(c)), "laplacian")
+        build = _lib.ek_laplacian_build_w if weighted else _lib.ek_laplacian_build
+        _chk(build(self._h, ctypes.byref(c)), "laplacian")
         return _take_csr(c)
 
-    def laplacian_rows(self, row0, row1):
-        """Rows [row0, row1) of the Laplacian (global columns, rowptr from 0): one rank's shard."""
+    def laplacian_rows(self, row0, row1, weighted=False):
+        """Rows [row0, row1) of the Laplacian (global columns, rowptr from 0): one rank's shard.  weighted: as
+        laplacian (ek_laplacian_build_rows_w)."""
         c = _P()
-        _chk(_lib.ek_laplacian_build_rows(self._h, int(row0), int(row1 - row0), ctypes.byref(c)), "laplacian_rows")
+        build = _lib.ek_laplacian_build_rows_w if weighted else _lib.ek_laplacian_build_rows
+        _chk(build(self._h, int(row0), int(row1 - row0), ctypes.byref(c)), "laplacian_rows")
         return _take_csr(c)
 
     def kl_graph(self):
@@ -879,13 +890,20 @@ class Context:
         _chk(_lib.ek_spmv_setup(self._c, int(n), int(row0), nrows, _p(rowptr), _p(col), _p(val)), "spmv_setup")
         self.n, self.nrows = int(n), nrows
 
-    def spmv_setup_pins(self, hgr):
+    def spmv_setup_pins(self, hgr, weighted=False):
         """This context's Laplacian rows assembled on the GPU from the pins (ek_spmv_setup_pins);
-        returns True when the device build ran (False: the host fallback)."""
+        returns True when the device build ran (False: the host fallback).  weighted: the net-weighted
+        Laplacian of Hypergraph.laplacian(weighted=True) (ek_spmv_setup_pins_w; no net weights: NULL, all ones)."""
         net_ptr, pins = hgr.pins()
         dev = ctypes.c_int32(0)
-        _chk(_lib.ek_spmv_setup_pins(self._c, hgr.nodes, len(net_ptr) - 1, _p(net_ptr), _p(pins), ctypes.byref(dev)),
-             "spmv_setup_pins")
+        if weighted:
+            net_w = hgr.weights()[1]
+            net_w = None if net_w is None else np.ascontiguousarray(net_w, np.int32)
+            _chk(_lib.ek_spmv_setup_pins_w(self._c, hgr.nodes, len(net_ptr) - 1, _p(net_ptr), _p(pins),
+                                           None if net_w is None else _p(net_w), ctypes.byref(dev)), "spmv_setup_pins_w")
+        else:
+            _chk(_lib.ek_spmv_setup_pins(self._c, hgr.nodes, len(net_ptr) - 1, _p(net_ptr), _p(pins),
+                                         ctypes.byref(dev)), "spmv_setup_pins")
         self.n, _, self.nrows = self.spmv_dims()
         return bool(dev.value)
 
@@ -1110,28 +1128,33 @@ class Context:
         return _match(lambda *a: _lib.ek_match(self._c, hgr._h, *a), "match", hgr, max_cluster, max_net, max_rounds)
 
     def multilevel_bipartition(self, hgr, imbalance=0.03, coarse_nodes=512, max_levels=ML_LEVELS, max_cluster=0,
-                               max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None):
+                               max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None,
+                               weighted_laplacian=False):
         """The multilevel bipartition (ek_multilevel_bipartition): matching and contraction down to coarse_nodes
         nodes, the weighted sweep cut of the coarsest level's Fiedler vector, the weighted FM refinement at every
         level.  max_cluster 0: from W, L_max and coarse_nodes.  lanczos: ek_lanczos_opts fields to override.
+        weighted_laplacian: the coarsest level's Laplacian carries its net weights (EK_ML_WEIGHTED_LAPLACIAN).
         Returns (side per node, result dict); the per-level lists of the dict hold levels + 1 entries."""
         o = _ml_opts(imbalance, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos)
         side = np.full(hgr.nodes, 255, np.uint8)
         r = MlResult()
-        _chk(_lib.ek_multilevel_bipartition(self._c, hgr._h, ctypes.byref(o), _p(side), ctypes.byref(r)),
-             "multilevel_bipartition")
+        _chk(_lib.ek_multilevel_bipartition_ex(self._c, hgr._h, ctypes.byref(o),
+                                               ML_WEIGHTED_LAPLACIAN if weighted_laplacian else 0, _p(side),
+                                               ctypes.byref(r)), "multilevel_bipartition")
         return side, _ml_result(r)
 
     def multilevel_bipartition_file(self, path, imbalance=0.03, coarse_nodes=512, out_dir=None, max_levels=ML_LEVELS,
-                                    max_cluster=0, max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None):
+                                    max_cluster=0, max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None,
+                                    weighted_laplacian=False):
         """The same on the hMETIS reading of a file, written to results/<base>.part.2 under out_dir
         (ek_multilevel_bipartition_file).  Returns (side per node, result dict)."""
         o = _ml_opts(imbalance, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos)
         side = np.full(Hypergraph.read_weighted(path).nodes, 255, np.uint8)
         r = MlResult()
-        _chk(_lib.ek_multilevel_bipartition_file(self._c, os.fsencode(path), ctypes.byref(o),
-                                                 os.fsencode(out_dir) if out_dir else None, _p(side), ctypes.byref(r)),
-             f"multilevel_bipartition_file {path}")
+        _chk(_lib.ek_multilevel_bipartition_file_ex(self._c, os.fsencode(path), ctypes.byref(o),
+                                                    os.fsencode(out_dir) if out_dir else None,
+                                                    ML_WEIGHTED_LAPLACIAN if weighted_laplacian else 0, _p(side),
+                                                    ctypes.byref(r)), f"multilevel_bipartition_file {path}")
         return side, _ml_result(r)
 
     def partition_kway_file(self, path, k, min_spectral=32, limit=-1, write_results=True, out_dir=None,

@@ -71,6 +71,10 @@
 //                        level's Fiedler vector, the weighted FM refinement at
 //                        every level (--fm-passes, --fm-stall apply) ->
 //                        results/<base>.part.2; one line beginning "ml:"
+//   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
+//                        carries its net weights (EK_ML_WEIGHTED_LAPLACIAN,
+//                        -(2 c(e) / |e|) per pin pair); the "ml:" line ends
+//                        with one more field, "wlap=1"
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -120,7 +124,7 @@ int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, 
 // multilevel.cpp: ek_multilevel_bipartition_file, for `--multilevel EPS`
 // (coarse_nodes <= 0, stall < 0: the defaults)
 int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, double imbalance, int coarse_nodes,
-                    int max_passes, int stall, ek_ml_result* r) __attribute__((weak));
+                    int max_passes, int stall, int32_t flags, ek_ml_result* r) __attribute__((weak));
 }
 
 namespace {
@@ -140,7 +144,8 @@ struct Opts {
     int fm_passes = 0, fm_stall = -1;  // (-1: the default)
     bool weighted = false;             // --weighted
     bool sweep_weighted = false, no_kl = false;  // --sweep-weighted, --no-kl
-    bool ml = false, ml_sub = false;  // --multilevel EPS; --ml-coarse seen
+    bool ml = false, ml_sub = false;  // --multilevel EPS; --ml-coarse or --ml-weighted-laplacian seen
+    bool ml_wlap = false;             // --ml-weighted-laplacian
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -447,7 +452,9 @@ int run_fm(const Opts& o) {
 constexpr const char* ML_USAGE =
     "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> [--ml-coarse <N>] [--fm-passes <P>] [--fm-stall <S>]  "
     "(--multilevel needs gKL2 and -EIG, and excludes --k, --sweep and --fm; --ml-coarse needs --multilevel; the file "
-    "is read as hMETIS reads it)\n";
+    "is read as hMETIS reads it)\n"
+    "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> --ml-weighted-laplacian  (the coarsest level's Laplacian "
+    "carries its net weights, -(2 c(e) / |e|) per pin pair; needs --multilevel; the ml: line ends with wlap=1)\n";
 
 // gKL2 <in.hgr> -EIG --multilevel EPS: one summary line beginning "ml:", results/<base>.part.2
 int run_ml(const Opts& o) {
@@ -456,16 +463,17 @@ int run_ml(const Opts& o) {
     const ek_solve_opts so = solve_opts(o);
     if (!ek::ml_file_for_cli) throw Fail{"this build carries no multilevel path"};
     ek_ml_result r{};
-    check(ek::ml_file_for_cli(ci.get(), o.input.c_str(), &so.lanczos, o.ml_eps, o.ml_coarse, o.fm_passes, o.fm_stall, &r),
+    check(ek::ml_file_for_cli(ci.get(), o.input.c_str(), &so.lanczos, o.ml_eps, o.ml_coarse, o.fm_passes, o.fm_stall,
+                              o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0, &r),
           "multilevel bipartition");
     std::printf("ml: imbalance %g, levels %d, coarsest_nodes %lld, max_cluster %lld, fallback %d, feasible %lld, "
                 "coarsest_cut %lld, cut %lld, cut_nets %lld, w0 %lld, w1 %lld, total_weight %lld, max_part %lld, n0 %lld, "
                 "n1 %lld, %.3f s (match %.3f, contract %.3f, lanczos %.3f, sweep %.3f, fm %.3f), %.3f s -> "
-                "results/%s.part.2\n", o.ml_eps, r.levels, (long long)r.nodes[r.levels], (long long)r.max_cluster,
+                "results/%s.part.2%s\n", o.ml_eps, r.levels, (long long)r.nodes[r.levels], (long long)r.max_cluster,
                 r.coarsest_fallback, (long long)r.sweep_feasible, (long long)r.cut_before[r.levels], (long long)r.cut,
                 (long long)r.cut_nets, (long long)r.w0, (long long)r.w1, (long long)r.total_weight, (long long)r.max_part,
                 (long long)r.n0, (long long)r.n1, r.t_total, r.t_match, r.t_contract, r.t_lanczos, r.t_sweep, r.t_fm,
-                secs(t0), base_name(o.input).c_str());
+                secs(t0), base_name(o.input).c_str(), o.ml_wlap ? ", wlap=1" : "");
     return 0;
 }
 
@@ -534,7 +542,7 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.ml_coarse = std::stoi(need("--ml-coarse"));
                 o.ml_sub = true;
                 if (o.ml_coarse < 1) throw Fail{"--ml-coarse takes a node count of at least 1"};
-            }
+            } else if (a == "--ml-weighted-laplacian") o.ml_wlap = o.ml_sub = true;
             else if (a == "--spectra") o.spectra = true;
             else if (a == "--reorth") {
                 const std::string v = need("--reorth");

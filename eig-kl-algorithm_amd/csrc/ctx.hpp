@@ -223,6 +223,7 @@ struct ek_ctx {
     // device build of the Laplacian rows (ek_spmv_setup_pins)
     DBuf lb_netptr, lb_pins, lb_icnt, lb_rcnt, lb_cur, lb_ip, lb_rp, lb_tiles, lb_inc, lb_scol, lb_sval, lb_tval,
         lb_ulen, lb_len, lb_diag, lb_long, lb_cnt, lb_off, lb_table, lb_flags, lb_codes;
+    DBuf lb_cw;  // the net weights beside the pins (ek_spmv_setup_pins_w)
     std::vector<hipEvent_t> spmv_ev;   // SpMV timing events, created once per context
     double* pin = nullptr;             // pinned host staging (Ritz vector + residual rows)
     size_t pin_doubles = 0;

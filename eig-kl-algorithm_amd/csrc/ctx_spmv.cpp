@@ -328,13 +328,20 @@ int ek_spmv_dims(ek_ctx* c, int64_t* n, int64_t* row0, int64_t* nrows) {
 // the body of ek_spmv_setup_pins; trusted_raw >= 0: the pins come from an
 // ek_hgr (every constructor validates them: ranges, monotone offsets) whose
 // reader counted the raw entries, so the two input scans (~0.25 ms at the
-// headline, bound by reading 4.3 MB) are skipped
+// headline, bound by reading 4.3 MB) are skipped.  net_w (nets values, or
+// null: the unweighted build and its kernels): the net-weighted Laplacian of
+// ek_spmv_setup_pins_w, on the device and in every fallback below;
+// trusted_w: an ek_hgr's weights, >= 1 by construction
 static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_t* net_ptr, const int32_t* pins,
-                                int32_t* on_device, int64_t trusted_raw) {
+                                const int32_t* net_w, bool trusted_w, int32_t* on_device, int64_t trusted_raw) {
     EK_TRY
     check_ctx(c);
     if (n <= 0 || n > INT32_MAX || nets < 0 || !net_ptr || (net_ptr[nets] > 0 && !pins) || net_ptr[0] != 0)
         ek::fail(EK_EINVAL, "ek_spmv_setup_pins: bad argument");
+    if (net_w && !trusted_w)
+        for (int64_t e = 0; e < nets; ++e)
+            if (net_w[e] < 1)
+                ek::fail(EK_EINVAL, "ek_spmv_setup_pins_w: weight %d of net %lld (>= 1)", net_w[e], (long long)e);
     const int64_t npins = net_ptr[nets];
     if (npins > INT32_MAX) ek::fail(EK_EINVAL, "ek_spmv_setup_pins: too many pins");
     ek::PhaseTimer pt("spmv_setup_pins");
@@ -368,8 +375,9 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
         h.nodes = n;
         h.net_ptr.assign(net_ptr, net_ptr + nets + 1);
         h.pins.assign(pins, pins + npins);
+        if (net_w) h.net_w.assign(net_w, net_w + nets);
         ek_csr L;
-        ek::build_laplacian_rows(h, row0, row0 + nrows, L);
+        ek::build_laplacian_rows(h, row0, row0 + nrows, L, net_w != nullptr);
         spmv_setup_rows(c, n, off, L.rowptr.data(), L.col.data(), L.val64.data());
         if (on_device) *on_device = 0;
     };
@@ -389,9 +397,11 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
     }
     pt.mark("input checks");
     {
-        Uploader up(c, s, (size_t(nets) + 1) * 8 + size_t(std::max<int64_t>(npins, 1)) * 4);
+        Uploader up(c, s, (size_t(nets) + 1) * 8 + size_t(std::max<int64_t>(npins, 1)) * 4 +
+                              (net_w ? size_t(std::max<int64_t>(nets, 1)) * 4 : 0));
         up.put(c->lb_netptr, net_ptr, size_t(nets) + 1);
         up.put(c->lb_pins, pins, size_t(npins));  // (no pins: an allocation all the same, nothing read from `pins`)
+        if (net_w) up.put(c->lb_cw, net_w, size_t(nets));
     }
     pt.mark("pins staged");
     const size_t nr = size_t(nrows);
@@ -401,6 +411,7 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
     b.r1 = row0 + nrows;
     b.net_ptr = c->lb_netptr.as<int64_t>();
     b.pins = c->lb_pins.as<int32_t>();
+    b.cw = net_w ? c->lb_cw.as<int32_t>() : nullptr;
     c->lb_icnt.ensure((nr + 1) * 4);
     c->lb_rcnt.ensure((nr + 1) * 4);
     c->lb_cur.ensure((nr + 1) * 4);
@@ -562,7 +573,12 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
 
 int ek_spmv_setup_pins(ek_ctx* c, int64_t n, int64_t nets, const int64_t* net_ptr, const int32_t* pins,
                        int32_t* on_device) {
-    return spmv_setup_pins_impl(c, n, nets, net_ptr, pins, on_device, -1);
+    return spmv_setup_pins_impl(c, n, nets, net_ptr, pins, nullptr, false, on_device, -1);
+}
+
+int ek_spmv_setup_pins_w(ek_ctx* c, int64_t n, int64_t nets, const int64_t* net_ptr, const int32_t* pins,
+                         const int32_t* net_w, int32_t* on_device) {
+    return spmv_setup_pins_impl(c, n, nets, net_ptr, pins, net_w, false, on_device, -1);
 }
 
 // x is the global n-vector; a sharded context reads it through its padded
@@ -784,6 +800,11 @@ namespace ek {
 // ek_spmv_setup_pins for an ek_hgr's pins (valid by construction), with the
 // raw-entry count its reader made when known
 int spmv_setup_hgr(ek_ctx* c, const ek_hgr& h, int32_t* on_device) {
-    return spmv_setup_pins_impl(c, h.nodes, h.nets, h.net_ptr.data(), h.pins.data(), on_device, h.raw_pairs);
+    return spmv_setup_pins_impl(c, h.nodes, h.nets, h.net_ptr.data(), h.pins.data(), nullptr, false, on_device,
+                                h.raw_pairs);
+}
+int spmv_setup_hgr_w(ek_ctx* c, const ek_hgr& h, int32_t* on_device) {
+    return spmv_setup_pins_impl(c, h.nodes, h.nets, h.net_ptr.data(), h.pins.data(),
+                                h.net_w.empty() ? nullptr : h.net_w.data(), true, on_device, h.raw_pairs);
 }
 }  // namespace ek

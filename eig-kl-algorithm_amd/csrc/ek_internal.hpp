@@ -97,6 +97,8 @@ struct ek_hgr {
 namespace ek {
 // ek_spmv_setup_pins for an ek_hgr (ctx_spmv.cpp): its pins need no range scan
 int spmv_setup_hgr(ek_ctx* c, const ek_hgr& h, int32_t* on_device);
+// ek_spmv_setup_pins_w the same way, with h's net weights (all ones when it carries none)
+int spmv_setup_hgr_w(ek_ctx* c, const ek_hgr& h, int32_t* on_device);
 }  // namespace ek
 
 struct ek_csr {
@@ -109,8 +111,10 @@ struct ek_csr {
 
 namespace ek {
 // graph_build.cpp
-void build_laplacian(const ek_hgr& h, ek_csr& out);
-void build_laplacian_rows(const ek_hgr& h, int64_t r0, int64_t r1, ek_csr& out);  // rows [r0, r1), global cols
+// (weighted: -(2 c(e) / |e|) per pin pair, c(e) = h's net weights: DESIGN.md §15)
+void build_laplacian(const ek_hgr& h, ek_csr& out, bool weighted = false);
+void build_laplacian_rows(const ek_hgr& h, int64_t r0, int64_t r1, ek_csr& out,
+                          bool weighted = false);  // rows [r0, r1), global cols
 void build_kl_graph(const ek_hgr& h, ek_csr& out);
 // libstdc++ unordered_map<uint32_t,...> iteration order for keys inserted
 // (first insertion) in the given order; writes the iteration order to out.
@@ -393,6 +397,7 @@ struct LapBuild {
     long long nets = 0, r0 = 0, r1 = 0;  // rows [r0, r1) of the global matrix
     const int64_t* net_ptr = nullptr;
     const int32_t* pins = nullptr;
+    const int32_t* cw = nullptr;  // net weights (ek_spmv_setup_pins_w); null: the unweighted kernels
     int *icnt = nullptr, *rcnt = nullptr, *cur = nullptr;  // per row: incidences, raw entries, fill cursor
     long long *ip = nullptr, *rp = nullptr;                // their exclusive scans (nr + 1)
     int32_t* inc = nullptr;                                // (net, position in net) pairs, by row

@@ -171,8 +171,13 @@ void hashtable_order_index(const uint32_t* keys, int64_t cnt, int32_t* out_idx, 
 // row ranges and write their rows to private buffers that are then copied into
 // place, so there is no per-row allocation.  Rows [r0, r1) only: the shard of
 // one rank of the sharded Lanczos (col keeps global ids).
-void build_laplacian_rows(const ek_hgr& h, int64_t r0, int64_t r1, ek_csr& L) {
+//
+// weighted: net e's term is -(2 c(e) / |e|), c(e) its net weight (DESIGN.md
+// §15); 2 c(e) <= 2^32 is exact in fp64, so the term is one rounded division,
+// and with c(e) = 1 (or no net weights) it is -(2.0 / |e|) bit for bit.
+void build_laplacian_rows(const ek_hgr& h, int64_t r0, int64_t r1, ek_csr& L, bool weighted) {
     const int64_t n = h.nodes, nr = r1 - r0;
+    const int32_t* cw = weighted && !h.net_w.empty() ? h.net_w.data() : nullptr;
     if (r0 < 0 || r1 > n || nr < 0) fail(EK_EINVAL, "Laplacian rows [%lld, %lld) outside [0, %lld)", (long long)r0,
                                          (long long)r1, (long long)n);
     PhaseTimer pt("laplacian");
@@ -257,7 +262,7 @@ void build_laplacian_rows(const ek_hgr& h, int64_t r0, int64_t r1, ek_csr& L) {
             row.clear();
             for (int64_t q = ip[size_t(i)]; q < ip[size_t(i) + 1]; ++q) {
                 const int64_t e = inc_net[size_t(q)], p0 = h.net_ptr[size_t(e)], p1 = h.net_ptr[size_t(e) + 1];
-                const double w = -(2.0 / double(p1 - p0));
+                const double w = -(double(2 * int64_t(cw ? cw[e] : 1)) / double(p1 - p0));
                 for (int64_t p = p0; p < p1; ++p)
                     if (p != inc[size_t(q)]) row.push_back({h.pins[size_t(p)], w});
             }
@@ -323,7 +328,7 @@ void build_laplacian_rows(const ek_hgr& h, int64_t r0, int64_t r1, ek_csr& L) {
     pt.mark("assemble");
 }
 
-void build_laplacian(const ek_hgr& h, ek_csr& L) { build_laplacian_rows(h, 0, h.nodes, L); }
+void build_laplacian(const ek_hgr& h, ek_csr& L, bool weighted) { build_laplacian_rows(h, 0, h.nodes, L, weighted); }
 
 // ---------------------------------------------------------------------------
 // cKL.cpp:107-131 + connections() order (cKL.cpp:229-248).
@@ -610,6 +615,26 @@ int ek_laplacian_build_rows(const ek_hgr* h, int64_t row0, int64_t nrows, ek_csr
     if (!h || !out || row0 < 0 || nrows < 0) ek::fail(EK_EINVAL, "ek_laplacian_build_rows: bad argument");
     auto c = std::make_unique<ek_csr>();
     ek::build_laplacian_rows(*h, row0, row0 + nrows, *c);
+    *out = c.release();
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_laplacian_build_w(const ek_hgr* h, ek_csr** out) {
+    EK_TRY
+    if (!h || !out) ek::fail(EK_EINVAL, "ek_laplacian_build_w: null argument");
+    auto c = std::make_unique<ek_csr>();
+    ek::build_laplacian(*h, *c, true);
+    *out = c.release();
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_laplacian_build_rows_w(const ek_hgr* h, int64_t row0, int64_t nrows, ek_csr** out) {
+    EK_TRY
+    if (!h || !out || row0 < 0 || nrows < 0) ek::fail(EK_EINVAL, "ek_laplacian_build_rows_w: bad argument");
+    auto c = std::make_unique<ek_csr>();
+    ek::build_laplacian_rows(*h, row0, row0 + nrows, *c, true);
     *out = c.release();
     return EK_OK;
     EK_CATCH

@@ -15,6 +15,7 @@
 //   k_net_fill    per net: (net, position) incidences into their rows' slots
 //   k_rows        per row: incidences sorted, raw entries gathered, stable
 //                 insertion sort by column, duplicates summed, diagonal
+//                 (<true>: the net-weighted term, ek_spmv_setup_pins_w; so k_rows_long)
 //   k_rows_long   one workgroup per row past k_rows' limit (LDS bitonic sort
 //                 of (column, index) keys: stable)
 //   k_row_write   per row: CSR columns / values, the diagonal in place
@@ -136,10 +137,15 @@ __global__ __launch_bounds__(BT) void k_net_fill(long long nets, const int64_t* 
 }
 
 // raw entries of row i in the host build's order: its incidences by (net,
-// position) ascending, each net's other pins in order; returns their count
+// position) ascending, each net's other pins in order; returns their count.
+// W: net e's term is -(2 cw[e] / |e|) (ek_spmv_setup_pins_w, DESIGN.md §15:
+// 2 cw[e] <= 2^32 is exact, so one rounded division as on the host); W = false
+// never reads cw and is the unweighted build as it was.
+template <bool W>
 __device__ int gather_row(long long i, const long long* __restrict__ ip, int2* __restrict__ inc,
-                          const int64_t* __restrict__ net_ptr, const int32_t* __restrict__ pins, int* __restrict__ scol,
-                          double* __restrict__ sval, long long at) {
+                          const int64_t* __restrict__ net_ptr, const int32_t* __restrict__ pins,
+                          const int32_t* __restrict__ cw, int* __restrict__ scol, double* __restrict__ sval,
+                          long long at) {
     const long long a = ip[i], b = ip[i + 1];
     for (long long x = a + 1; x < b; ++x) {  // atomics filled the slots in any order
         const int2 key = inc[x];
@@ -154,7 +160,7 @@ __device__ int gather_row(long long i, const long long* __restrict__ ip, int2* _
     for (long long x = a; x < b; ++x) {
         const int2 q = inc[x];
         const long long p0 = net_ptr[q.x], p1 = net_ptr[q.x + 1];
-        const double w = -(2.0 / double(p1 - p0));
+        const double w = W ? -(double(2 * (long long)cw[q.x]) / double(p1 - p0)) : -(2.0 / double(p1 - p0));
         for (long long p = p0; p < p1; ++p)
             if (p - p0 != q.y) {
                 scol[at + m] = pins[p];
@@ -190,13 +196,14 @@ __device__ void merge_row(long long i, long long r, int* __restrict__ scol, doub
     diag[i] = -s;
 }
 
+template <bool W>
 __global__ __launch_bounds__(BT) void k_rows(long long nr, long long r0, const long long* __restrict__ ip,
                                              int2* __restrict__ inc, const long long* __restrict__ rp,
                                              const int64_t* __restrict__ net_ptr, const int32_t* __restrict__ pins,
                                              int* __restrict__ scol, double* __restrict__ sval, int* __restrict__ ulen,
                                              int* __restrict__ len, double* __restrict__ diag,
                                              int* __restrict__ long_rows, int* __restrict__ n_long,
-                                             int* __restrict__ too_long) {
+                                             int* __restrict__ too_long, const int32_t* __restrict__ cw) {
     const long long i = (long long)blockIdx.x * BT + threadIdx.x;
     if (i >= nr) return;
     const long long at = rp[i];
@@ -208,7 +215,7 @@ __global__ __launch_bounds__(BT) void k_rows(long long nr, long long r0, const l
         long_rows[atomicAdd(n_long, 1)] = int(i);
         return;
     }
-    const int m = gather_row(i, ip, inc, net_ptr, pins, scol, sval, at);
+    const int m = gather_row<W>(i, ip, inc, net_ptr, pins, cw, scol, sval, at);
     for (int x = 1; x < m; ++x) {  // stable insertion sort by column
         const int c = scol[at + x];
         const double v = sval[at + x];
@@ -224,13 +231,15 @@ __global__ __launch_bounds__(BT) void k_rows(long long nr, long long r0, const l
     merge_row(i, r0 + i, scol, sval, at, m, ulen, len, diag);
 }
 
+template <bool W>
 __global__ __launch_bounds__(BT) void k_rows_long(long long r0, const int* __restrict__ long_rows,
                                                   const long long* __restrict__ ip, int2* __restrict__ inc,
                                                   const long long* __restrict__ rp, const int64_t* __restrict__ net_ptr,
                                                   const int32_t* __restrict__ pins, int* __restrict__ scol,
                                                   double* __restrict__ sval, double* __restrict__ tval,
                                                   int* __restrict__ ulen, int* __restrict__ len,
-                                                  double* __restrict__ diag, int* __restrict__ too_long) {
+                                                  double* __restrict__ diag, int* __restrict__ too_long,
+                                                  const int32_t* __restrict__ cw) {
     __shared__ unsigned long long key[LONG_CAP];
     __shared__ int m_s;
     const long long i = long_rows[blockIdx.x];
@@ -239,7 +248,7 @@ __global__ __launch_bounds__(BT) void k_rows_long(long long r0, const int* __res
         if (threadIdx.x == 0) atomicAdd(too_long, 1);
         return;
     }
-    if (threadIdx.x == 0) m_s = gather_row(i, ip, inc, net_ptr, pins, scol, sval, at);
+    if (threadIdx.x == 0) m_s = gather_row<W>(i, ip, inc, net_ptr, pins, cw, scol, sval, at);
     __syncthreads();
     const int m = m_s;
     int p2 = 1;
@@ -429,16 +438,17 @@ void lap_fill_rows(hipStream_t s, const LapBuild& b) {
     if (b.nets > 0)
         hipLaunchKernelGGL(k_net_fill, dim3(grid_of(b.nets)), dim3(BT), 0, s, b.nets, b.net_ptr, b.pins, b.r0, b.r1,
                            b.ip, b.cur, inc);
-    if (nr > 0)
-        hipLaunchKernelGGL(k_rows, dim3(grid_of(nr)), dim3(BT), 0, s, nr, b.r0, b.ip, inc, b.rp, b.net_ptr, b.pins,
-                           b.scol, b.sval, b.ulen, b.len, b.diag, b.long_rows, b.counters, b.counters + 1);
+    if (nr <= 0) return;
+    const auto k = b.cw ? k_rows<true> : k_rows<false>;
+    hipLaunchKernelGGL(k, dim3(grid_of(nr)), dim3(BT), 0, s, nr, b.r0, b.ip, inc, b.rp, b.net_ptr, b.pins, b.scol,
+                       b.sval, b.ulen, b.len, b.diag, b.long_rows, b.counters, b.counters + 1, b.cw);
 }
 
 void lap_long_rows(hipStream_t s, const LapBuild& b, int n_long) {
-    if (n_long > 0)
-        hipLaunchKernelGGL(k_rows_long, dim3(n_long), dim3(BT), 0, s, b.r0, b.long_rows, b.ip,
-                           reinterpret_cast<int2*>(b.inc), b.rp, b.net_ptr,
-                           b.pins, b.scol, b.sval, b.tval, b.ulen, b.len, b.diag, b.counters + 1);
+    if (n_long <= 0) return;
+    const auto k = b.cw ? k_rows_long<true> : k_rows_long<false>;
+    hipLaunchKernelGGL(k, dim3(n_long), dim3(BT), 0, s, b.r0, b.long_rows, b.ip, reinterpret_cast<int2*>(b.inc), b.rp,
+                       b.net_ptr, b.pins, b.scol, b.sval, b.tval, b.ulen, b.len, b.diag, b.counters + 1, b.cw);
 }
 
 void lap_write(hipStream_t s, const LapBuild& b, const long long* off, int* rowptr, int* col, double* val) {

@@ -26,8 +26,13 @@ void chk(int rc) {
 
 using Hgr = std::unique_ptr<ek_hgr, void (*)(ek_hgr*)>;
 
-void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, uint8_t* side_out, ek_ml_result* result) {
+// flags & EK_ML_WEIGHTED_LAPLACIAN: the coarsest level's Laplacian carries H_L's
+// net weights (ek_spmv_setup_pins_w); nothing else changes
+void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, int32_t flags, uint8_t* side_out,
+                 ek_ml_result* result) {
     const auto t0 = clk::now();
+    if (flags & ~int32_t(EK_ML_WEIGHTED_LAPLACIAN))
+        ek::fail(EK_EINVAL, "ek_multilevel_bipartition_ex: unknown flag bits 0x%x", unsigned(flags));
     ek_ml_opts o;
     ek_ml_default_opts(&o);
     if (opts) o = *opts;
@@ -86,7 +91,8 @@ void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, uint8_t* 
     bool spectral = edges && nc >= (o.lanczos.deflate ? 4 : 6);  // (below it ek_lanczos_fiedler answers EK_EINVAL)
     if (spectral) {
         const auto t = clk::now();
-        chk(ek_spmv_setup_pins(ctx, nc, cur->nets, cur->net_ptr.data(), cur->pins.data(), nullptr));
+        if (flags & EK_ML_WEIGHTED_LAPLACIAN) chk(ek::spmv_setup_hgr_w(ctx, *cur, nullptr));
+        else chk(ek_spmv_setup_pins(ctx, nc, cur->nets, cur->net_ptr.data(), cur->pins.data(), nullptr));
         double lambda = 0.0;
         ek_lanczos_stats st{};
         const int rc = ek_lanczos_fiedler(ctx, &o.lanczos, &lambda, v.data(), &st);
@@ -141,11 +147,12 @@ void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, uint8_t* 
 }  // namespace
 
 namespace ek {
-// `gKL2 <in> -EIG --multilevel EPS` (cli.cpp refers to it weakly); coarse_nodes <= 0, stall < 0: the defaults
+// `gKL2 <in> -EIG --multilevel EPS [--ml-weighted-laplacian]` (cli.cpp refers to it weakly); coarse_nodes <= 0,
+// stall < 0: the defaults; flags: ek_multilevel_bipartition_file_ex's
 int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, double imbalance, int coarse_nodes,
-                    int max_passes, int stall, ek_ml_result* r);
+                    int max_passes, int stall, int32_t flags, ek_ml_result* r);
 int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, double imbalance, int coarse_nodes,
-                    int max_passes, int stall, ek_ml_result* r) {
+                    int max_passes, int stall, int32_t flags, ek_ml_result* r) {
     ek_ml_opts o;
     ek_ml_default_opts(&o);
     o.imbalance = imbalance;
@@ -153,7 +160,7 @@ int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczo
     o.fm.max_passes = max_passes;
     if (stall >= 0) o.fm.stall = stall;
     if (lanczos) o.lanczos = *lanczos;
-    return ek_multilevel_bipartition_file(ctx, path, &o, nullptr, nullptr, r);
+    return ek_multilevel_bipartition_file_ex(ctx, path, &o, nullptr, flags, nullptr, r);
 }
 }  // namespace ek
 
@@ -173,15 +180,25 @@ void ek_ml_default_opts(ek_ml_opts* o) {
 
 int ek_multilevel_bipartition(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* opts, uint8_t* side_out,
                               ek_ml_result* result) {
+    return ek_multilevel_bipartition_ex(ctx, h, opts, 0, side_out, result);
+}
+
+int ek_multilevel_bipartition_ex(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* opts, int32_t flags, uint8_t* side_out,
+                                 ek_ml_result* result) {
     EK_TRY
     if (!ctx || !h || (h->nodes > 0 && !side_out)) ek::fail(EK_EINVAL, "ek_multilevel_bipartition: null argument");
-    bipartition(ctx, *h, opts, side_out, result);
+    bipartition(ctx, *h, opts, flags, side_out, result);
     return EK_OK;
     EK_CATCH
 }
 
 int ek_multilevel_bipartition_file(ek_ctx* ctx, const char* path, const ek_ml_opts* opts, const char* out_dir,
                                    uint8_t* side_out, ek_ml_result* result) {
+    return ek_multilevel_bipartition_file_ex(ctx, path, opts, out_dir, 0, side_out, result);
+}
+
+int ek_multilevel_bipartition_file_ex(ek_ctx* ctx, const char* path, const ek_ml_opts* opts, const char* out_dir,
+                                      int32_t flags, uint8_t* side_out, ek_ml_result* result) {
     EK_TRY
     if (!ctx || !path) ek::fail(EK_EINVAL, "ek_multilevel_bipartition_file: null argument");
     ek_hgr* h = nullptr;
@@ -192,7 +209,7 @@ int ek_multilevel_bipartition_file(ek_ctx* ctx, const char* path, const ek_ml_op
         own.resize(size_t(h->nodes));
         side_out = own.data();
     }
-    bipartition(ctx, *h, opts, side_out, result);
+    bipartition(ctx, *h, opts, flags, side_out, result);
     const std::vector<int32_t> part(side_out, side_out + h->nodes);
     ek::write_part_file(path, out_dir, 2, h->nodes, part.data());
     return EK_OK;

@@ -124,6 +124,17 @@ int ek_laplacian_build(const ek_hgr* h, ek_csr** out);
 /* Rows [row0, row0+nrows) only (global column ids): one rank's shard of the
  * sharded Lanczos, as ek_shard_rows assigns it. */
 int ek_laplacian_build_rows(const ek_hgr* h, int64_t row0, int64_t nrows, ek_csr** out);
+/* The net-weighted clique Laplacian: ek_laplacian_build[_rows]
+ * with one replacement — a net e of k = |e| >= 2 pins (repeated pins counted)
+ * gives each ordered pin pair the fp64 value -(double(2 c(e)) / double(k)),
+ * c(e) = h's net weight (1 where h carries none), in place of -(2.0 / k).
+ * 2 c(e) <= 2^32 is exact, so the value is one correctly rounded division;
+ * with c(e) = 1 it is the unweighted value bit for bit, and on an h without
+ * net weights these return the arrays of ek_laplacian_build[_rows].  Order of
+ * the sums, diagonal, isolated rows: as there.  Node weights do not enter.
+ * No reference counterpart. */
+int ek_laplacian_build_w(const ek_hgr* h, ek_csr** out);
+int ek_laplacian_build_rows_w(const ek_hgr* h, int64_t row0, int64_t nrows, ek_csr** out);
 /* fp32 KL adjacency, w = 1/(|e|-1) accumulated in net order; each row holds
  * its forward (upper-triangle) entries in the iteration order of cKL's
  * std::unordered_map<uint32_t,float> (libstdc++ _Hashtable, emulated), then
@@ -203,6 +214,16 @@ int ek_spmv_setup(ek_ctx* ctx, int64_t n, int64_t row0, int64_t nrows, const int
  * tells which ran. */
 int ek_spmv_setup_pins(ek_ctx* ctx, int64_t n, int64_t nets, const int64_t* net_ptr, const int32_t* pins,
                        int32_t* on_device);
+/* ek_spmv_setup_pins for the net-weighted Laplacian of ek_laplacian_build_w:
+ * net_w holds nets values >= 1 (EK_EINVAL otherwise); NULL stands for all
+ * ones and is ek_spmv_setup_pins exactly.  Bit-identical to ek_spmv_setup on
+ * the rows of ek_laplacian_build_rows_w; every fallback (a row past the
+ * device sort, EK_HOST_LAPLACIAN, EK_SPMV_PLAIN, a value set that outgrows
+ * the dictionary -> plain CSR) carries the weights.  The shard map of a
+ * multi-rank context stays ek_shard_map's: structural, the same on every
+ * rank. */
+int ek_spmv_setup_pins_w(ek_ctx* ctx, int64_t n, int64_t nets, const int64_t* net_ptr, const int32_t* pins,
+                         const int32_t* net_w /* nets values >= 1; NULL: all ones */, int32_t* on_device);
 /* The rows the context owns after the last ek_spmv_setup (any of the
  * pointers may be NULL). */
 int ek_spmv_dims(ek_ctx* ctx, int64_t* n, int64_t* row0, int64_t* nrows);
@@ -965,6 +986,16 @@ int ek_multilevel_bipartition(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* op
  * node order.  side_out may be NULL. */
 int ek_multilevel_bipartition_file(ek_ctx* ctx, const char* path, const ek_ml_opts* opts, const char* out_dir,
                                    uint8_t* side_out, ek_ml_result* result);
+/* As the two above.  flags = 0: exactly they.  flags & EK_ML_WEIGHTED_LAPLACIAN:
+ * the coarsest level's ek_spmv_setup_pins is ek_spmv_setup_pins_w with H_L's
+ * net weights (the summed c(e) of the nets ek_hgr_contract merged), so Lanczos
+ * sees them; nothing else in the V-cycle changes.  EK_EINVAL for any other
+ * flag bit. */
+#define EK_ML_WEIGHTED_LAPLACIAN 1
+int ek_multilevel_bipartition_ex(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* opts, int32_t flags,
+                                 uint8_t* side_out /* nodes */, ek_ml_result* result);
+int ek_multilevel_bipartition_file_ex(ek_ctx* ctx, const char* path, const ek_ml_opts* opts, const char* out_dir,
+                                      int32_t flags, uint8_t* side_out, ek_ml_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
