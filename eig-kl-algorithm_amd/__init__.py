@@ -196,6 +196,40 @@ class MlResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _ML_TIMES])
 
 
+class SweepWBResult(_AbiStruct):
+    """eigkl.h ek_sweep_wb_result (the weighted sweep cut under per-side bounds)."""
+    _fields_ = ([(k, _I64) for k in ("n", "n0", "n1", "s_lo", "s_hi", "feasible", "total_weight", "bound0", "bound1",
+                                     "w0", "w1", "cut", "cut_nets", "cut_half", "spanning_nets")]
+                + [(k, ctypes.c_double) for k in _SWEEP_TIMES])
+
+
+class FmWBResult(_AbiStruct):
+    """eigkl.h ek_fm_wb_result (the weighted FM refinement under per-side bounds)."""
+    _fields_ = ([("n", _I64), ("total_weight", _I64), ("bound0", _I64), ("bound1", _I64), ("passes", _I32),
+                 ("passes_run", _I32)]
+                + [(k, _I64) for k in ("moves_tried", "moves_kept", "cut_before", "cut", "cut_nets_before", "cut_nets",
+                                       "w0", "w1", "n0", "n1")]
+                + [(k, ctypes.c_double) for k in _FM_TIMES])
+
+
+class KwayMlOpts(_AbiStruct):
+    """eigkl.h ek_kway_ml_opts."""
+    _fields_ = [("k", _I32), ("flags", _I32), ("imbalance", ctypes.c_double), ("write_results", _I32), ("pad", _I32),
+                ("out_dir", ctypes.c_char_p), ("ml", MlOpts)]
+
+
+_KWAY_ML_INTS = ("total_weight", "part_bound", "part_w_min", "part_w_max", "parts_over_bound", "empty_parts", "cut_nets",
+                 "connectivity", "connectivity_w", "soed", "levels_total", "fm_moves")
+_KWAY_ML_TIMES = ("t_induce", "t_ml", "t_metrics", "t_total", "t_match", "t_contract", "t_lanczos", "t_sweep", "t_fm")
+
+
+class KwayMlResult(_AbiStruct):
+    """eigkl.h ek_kway_ml_result."""
+    _fields_ = ([("k", _I32), ("bisections", _I32), ("coarsest_fallbacks", _I32), ("infeasible_sweeps", _I32)]
+                + [(k, _I64) for k in _KWAY_ML_INTS] + [(k, ctypes.c_double) for k in _KWAY_ML_TIMES]
+                + [("t_level", ctypes.c_double * KWAY_LEVELS)])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -337,6 +371,22 @@ _sig("ek_multilevel_bipartition_ex", ctypes.c_int, _P, _P, ctypes.POINTER(MlOpts
 _sig("ek_multilevel_bipartition_file_ex", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(MlOpts), ctypes.c_char_p,
      _I32, _P, ctypes.POINTER(MlResult))
 ML_WEIGHTED_LAPLACIAN = 1  # eigkl.h EK_ML_WEIGHTED_LAPLACIAN
+_sig("ek_sweep_cut_wb_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, _P, _P,
+     ctypes.POINTER(SweepWBResult))
+_sig("ek_sweep_cut_wb", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, _P, _P,
+     ctypes.POINTER(SweepWBResult))
+_sig("ek_fm_refine_wb_host", ctypes.c_int, _P, ctypes.POINTER(FmOpts), _P, _P, _P, _I64, _P, _I64,
+     ctypes.POINTER(FmWBResult))
+_sig("ek_fm_refine_wb", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _P, _I64, _P, _I64,
+     ctypes.POINTER(FmWBResult))
+_sig("ek_multilevel_bipartition_b", ctypes.c_int, _P, _P, ctypes.POINTER(MlOpts), _I32, _P, _P, ctypes.POINTER(MlResult))
+_sig("ek_kway_bisect_bounds", ctypes.c_int, _I64, _I32, _I64, ctypes.c_double, _P)
+_sig("ek_kway_metrics_w_host", ctypes.c_int, _P, _P, _I32, _P)
+_sig("ek_kway_metrics_w", ctypes.c_int, _P, _P, _P, _I32, _P)
+_sig("ek_kway_ml_default_opts", None, ctypes.POINTER(KwayMlOpts))
+_sig("ek_partition_kway_ml", ctypes.c_int, _P, _P, ctypes.POINTER(KwayMlOpts), _P, ctypes.POINTER(KwayMlResult))
+_sig("ek_partition_kway_ml_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayMlOpts), _P,
+     ctypes.POINTER(KwayMlResult))
 
 lib = _lib
 
@@ -660,7 +710,8 @@ def _sweep_w_result(r):
     return {name: getattr(r, name) for name, _ in SweepWResult._fields_}
 
 
-def _sweep_cut_w(call, what, hgr, v, imbalance):
+def _sweep_cut_w(call, what, hgr, v, imbalance, result_type=None):
+    result_type = result_type or SweepWResult
     v = np.ascontiguousarray(v, np.float64)
     if len(v) != hgr.nodes:
         raise ValueError(f"v has {len(v)} entries for {hgr.nodes} nodes")
@@ -668,9 +719,9 @@ def _sweep_cut_w(call, what, hgr, v, imbalance):
     order = np.full(len(v), -1, np.int32)
     profile = np.full(len(v) + 1, -1, np.int64)
     prefix = np.full(len(v) + 1, -1, np.int64)
-    r = SweepWResult()
+    r = result_type()
     _chk(call(_p(v), ctypes.byref(o), _p(order), _p(profile), _p(prefix), ctypes.byref(r)), what)
-    return _sweep_w_result(r), order, profile, prefix
+    return {name: getattr(r, name) for name, _ in result_type._fields_}, order, profile, prefix
 
 
 def sweep_cut_w_host(hgr, v, imbalance=0.03):
@@ -680,6 +731,70 @@ def sweep_cut_w_host(hgr, v, imbalance=0.03):
     Returns (result dict, order, profile_w, prefix): order[r] the node at rank r, profile_w[s] the weight of the
     nets cut by split s, prefix[s] the weight of side 1 of split s (int64 both)."""
     return _sweep_cut_w(lambda *a: _lib.ek_sweep_cut_w_host(hgr._h, *a), "sweep_cut_w_host", hgr, v, imbalance)
+
+
+def _bounds(bounds):
+    b = np.ascontiguousarray(bounds, np.int64)
+    if b.shape != (2,):
+        raise ValueError("bounds: the two sides' greatest weights (L0, L1)")
+    return b
+
+
+def sweep_cut_wb_host(hgr, v, bounds):
+    """sweep_cut_w_host under per-side bounds (ek_sweep_cut_wb_host): side 0 may weigh at most bounds[0], side 1
+    (the low ranks) at most bounds[1]; the balance key is the slack difference.  Returns (result dict, order,
+    profile_w, prefix)."""
+    b = _bounds(bounds)
+    return _sweep_cut_w(lambda v_, o, *a: _lib.ek_sweep_cut_wb_host(hgr._h, v_, o, _p(b), *a), "sweep_cut_wb_host", hgr, v,
+                        0.0, SweepWBResult)
+
+
+def fm_refine_wb_host(hgr, side, bounds, max_passes=0, stall=1000, move_cap=None):
+    """fm_refine_w_host under per-side bounds (ek_fm_refine_wb_host): side s may hold at most bounds[s]; a pass_log
+    row ends with the slack difference.  Returns (side, pass_log, move_log, result dict)."""
+    b = _bounds(bounds)
+    return _fm_refine(lambda o, *a: _lib.ek_fm_refine_wb_host(hgr._h, o, _p(b), *a), "fm_refine_wb_host", hgr, side, 0.0,
+                      max_passes, stall, move_cap, FmWBResult)
+
+
+def kway_bisect_bounds(Wb, kb, part_bound, mult):
+    """(L0, L1) of one bisection of the k-way recursion (ek_kway_bisect_bounds)."""
+    out = np.zeros(2, np.int64)
+    _chk(_lib.ek_kway_bisect_bounds(int(Wb), int(kb), int(part_bound), float(mult), _p(out)), "kway_bisect_bounds")
+    return int(out[0]), int(out[1])
+
+
+def _kway_metrics_w(call, what, hgr, part, k):
+    part = np.ascontiguousarray(part, np.int32)
+    if len(part) != hgr.nodes:
+        raise ValueError(f"part has {len(part)} entries for {hgr.nodes} nodes")
+    out = np.zeros(4 + max(int(k), 0), np.int64)
+    _chk(call(_p(part), int(k), _p(out)), what)
+    return tuple(int(x) for x in out[:4]), out[4:].copy()
+
+
+def kway_metrics_w_host(hgr, part, k):
+    """((cut nets, connectivity, weighted connectivity, SOED), part weights) of a part vector under hgr's weights
+    (ek_kway_metrics_w_host)."""
+    return _kway_metrics_w(lambda *a: _lib.ek_kway_metrics_w_host(hgr._h, *a), "kway_metrics_w_host", hgr, part, k)
+
+
+def _kway_ml_opts(k, imbalance, coarse_nodes, weighted_laplacian, write_results, out_dir, max_passes, stall, lanczos):
+    o = KwayMlOpts()
+    _lib.ek_kway_ml_default_opts(ctypes.byref(o))
+    o.k, o.imbalance, o.flags = int(k), float(imbalance), ML_WEIGHTED_LAPLACIAN if weighted_laplacian else 0
+    o.write_results = 1 if write_results else 0
+    o.out_dir = os.fsencode(out_dir) if out_dir else None
+    o.ml.coarse_nodes, o.ml.fm.max_passes, o.ml.fm.stall = int(coarse_nodes), int(max_passes), int(stall)
+    for name, val in (lanczos or {}).items():
+        setattr(o.ml.lanczos, name, val)
+    return o
+
+
+def _kway_ml_result(r):
+    out = {k: getattr(r, k) for k, _ in KwayMlResult._fields_ if k != "t_level"}
+    out["t_level"] = list(r.t_level)
+    return out
 
 
 def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap, result_type=None):
@@ -1076,6 +1191,59 @@ class Context:
              "kl_set_partition_fiedler_sweep_w")
         self._n01 = (r.n0, r.n1)
         return _sweep_w_result(r)
+
+    def sweep_cut_wb(self, hgr, v, bounds):
+        """sweep_cut_wb_host on the GPU (ek_sweep_cut_wb): the same order, profile_w, prefix and result integers."""
+        b = _bounds(bounds)
+        return _sweep_cut_w(lambda v_, o, *a: _lib.ek_sweep_cut_wb(self._c, hgr._h, v_, o, _p(b), *a), "sweep_cut_wb",
+                            hgr, v, 0.0, SweepWBResult)
+
+    def fm_refine_wb(self, hgr, side, bounds, max_passes=0, stall=1000, move_cap=None):
+        """fm_refine_wb_host on the GPU (ek_fm_refine_wb): the same sides, logs and result integers."""
+        b = _bounds(bounds)
+        return _fm_refine(lambda o, *a: _lib.ek_fm_refine_wb(self._c, hgr._h, o, _p(b), *a), "fm_refine_wb", hgr, side,
+                          0.0, max_passes, stall, move_cap, FmWBResult)
+
+    def multilevel_bipartition_b(self, hgr, bounds, coarse_nodes=512, max_levels=ML_LEVELS, max_cluster=0, max_net=64,
+                                 max_rounds=8, max_passes=0, stall=1000, lanczos=None, weighted_laplacian=False):
+        """multilevel_bipartition under per-side bounds (ek_multilevel_bipartition_b): side s ends with at most
+        bounds[s] when the coarsest sweep is feasible.  Returns (side per node, result dict); max_part reports
+        max(bounds)."""
+        b = _bounds(bounds)
+        o = _ml_opts(0.0, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos)
+        side = np.full(hgr.nodes, 255, np.uint8)
+        r = MlResult()
+        _chk(_lib.ek_multilevel_bipartition_b(self._c, hgr._h, ctypes.byref(o),
+                                              ML_WEIGHTED_LAPLACIAN if weighted_laplacian else 0, _p(b), _p(side),
+                                              ctypes.byref(r)), "multilevel_bipartition_b")
+        return side, _ml_result(r)
+
+    def kway_metrics_w(self, hgr, part, k):
+        """kway_metrics_w_host on the GPU (ek_kway_metrics_w)."""
+        return _kway_metrics_w(lambda *a: _lib.ek_kway_metrics_w(self._c, hgr._h, *a), "kway_metrics_w", hgr, part, k)
+
+    def partition_kway_ml(self, hgr, k, imbalance=0.03, coarse_nodes=512, weighted_laplacian=False, max_passes=0,
+                          stall=1000, lanczos=None):
+        """k-way partition by recursive multilevel bisection under per-side weight bounds (ek_partition_kway_ml):
+        every part weighs at most floor((1 + imbalance) ceil(W / k)) under unit node weights.  Returns (part id per
+        node, result dict)."""
+        o = _kway_ml_opts(k, imbalance, coarse_nodes, weighted_laplacian, False, None, max_passes, stall, lanczos)
+        part = np.full(hgr.nodes, -1, np.int32)
+        r = KwayMlResult()
+        _chk(_lib.ek_partition_kway_ml(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)), "partition_kway_ml")
+        return part, _kway_ml_result(r)
+
+    def partition_kway_ml_file(self, path, k, imbalance=0.03, coarse_nodes=512, weighted_laplacian=False,
+                               write_results=True, out_dir=None, max_passes=0, stall=1000, lanczos=None):
+        """The same on the hMETIS reading of a file; write_results: results/<base>.part.<k> under out_dir
+        (ek_partition_kway_ml_file).  Returns (part id per node, result dict)."""
+        o = _kway_ml_opts(k, imbalance, coarse_nodes, weighted_laplacian, write_results, out_dir, max_passes, stall,
+                          lanczos)
+        part = np.full(Hypergraph.read_weighted(path).nodes, -1, np.int32)
+        r = KwayMlResult()
+        _chk(_lib.ek_partition_kway_ml_file(self._c, os.fsencode(path), ctypes.byref(o), _p(part), ctypes.byref(r)),
+             f"partition_kway_ml_file {path}")
+        return part, _kway_ml_result(r)
 
     def rank_split_device(self, v, n1):
         """rank_split run by the device kernels on an uploaded copy of v (ek_rank_split_device)."""

@@ -71,6 +71,14 @@
 //                        level's Fiedler vector, the weighted FM refinement at
 //                        every level (--fm-passes, --fm-stall apply) ->
 //                        results/<base>.part.2; one line beginning "ml:"
+//   --kway-multilevel EPS  gKL2 <in.hgr> -EIG --k N only, in place of
+//                        --multilevel (which keeps refusing --k), not with
+//                        --refine: the N-way partition by recursive multilevel
+//                        bisection under per-side weight bounds
+//                        (ek_partition_kway_ml_file) with imbalance EPS;
+//                        --ml-coarse, --ml-weighted-laplacian, --fm-passes and
+//                        --fm-stall apply -> results/<base>.part.<N>; one line
+//                        beginning "k-way-ml:"
 //   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
 //                        carries its net weights (EK_ML_WEIGHTED_LAPLACIAN,
 //                        -(2 c(e) / |e|) per pin pair); the "ml:" line ends
@@ -125,6 +133,10 @@ int sweepw_file_for_cli(ek_ctx* ctx, const char* path, const ek_solve_opts* so, 
 // (coarse_nodes <= 0, stall < 0: the defaults)
 int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczos, double imbalance, int coarse_nodes,
                     int max_passes, int stall, int32_t flags, ek_ml_result* r) __attribute__((weak));
+// kway_ml.cpp: ek_partition_kway_ml_file with the results file on, for `--k N --kway-multilevel EPS`
+int kway_ml_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                         int coarse_nodes, int max_passes, int stall, int32_t flags, ek_kway_ml_result* r)
+    __attribute__((weak));
 }
 
 namespace {
@@ -146,6 +158,7 @@ struct Opts {
     bool sweep_weighted = false, no_kl = false;  // --sweep-weighted, --no-kl
     bool ml = false, ml_sub = false;  // --multilevel EPS; --ml-coarse or --ml-weighted-laplacian seen
     bool ml_wlap = false;             // --ml-weighted-laplacian
+    bool kml = false;                 // --kway-multilevel EPS (sets ml and ml_eps too): with --k, the k-way driver
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -453,6 +466,9 @@ constexpr const char* ML_USAGE =
     "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> [--ml-coarse <N>] [--fm-passes <P>] [--fm-stall <S>]  "
     "(--multilevel needs gKL2 and -EIG, and excludes --k, --sweep and --fm; --ml-coarse needs --multilevel; the file "
     "is read as hMETIS reads it)\n"
+    "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> [--ml-coarse <N>] "
+    "[--ml-weighted-laplacian]  (the k-way partition by recursive multilevel bisection; needs --k with 2 <= parts <= "
+    "256, excludes --multilevel and --refine)\n"
     "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> --ml-weighted-laplacian  (the coarsest level's Laplacian "
     "carries its net weights, -(2 c(e) / |e|) per pin pair; needs --multilevel; the ml: line ends with wlap=1)\n";
 
@@ -474,6 +490,29 @@ int run_ml(const Opts& o) {
                 (long long)r.cut_nets, (long long)r.w0, (long long)r.w1, (long long)r.total_weight, (long long)r.max_part,
                 (long long)r.n0, (long long)r.n1, r.t_total, r.t_match, r.t_contract, r.t_lanczos, r.t_sweep, r.t_fm,
                 secs(t0), base_name(o.input).c_str(), o.ml_wlap ? ", wlap=1" : "");
+    return 0;
+}
+
+// gKL2 <in.hgr> -EIG --k N --kway-multilevel EPS: one summary line beginning "k-way-ml:", results/<base>.part.<N>
+int run_kway_ml(const Opts& o) {
+    const auto t0 = clk::now();
+    CtxInit ci(o.device, o.teardown);
+    const ek_solve_opts so = solve_opts(o);
+    if (!ek::kway_ml_file_for_cli) throw Fail{"this build carries no multilevel k-way path"};
+    ek_kway_ml_result r{};
+    check(ek::kway_ml_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse, o.fm_passes,
+                                   o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0, &r),
+          "multilevel k-way partition");
+    std::printf("k-way-ml: k %d, imbalance %g, bisections %d, fallbacks %d, infeasible %d, total_weight %lld, part_bound "
+                "%lld, part weights %lld..%lld, over_bound %lld, empty %lld, cut nets %lld, connectivity %lld, "
+                "connectivity_w %lld, SOED %lld, levels %lld, fm_moves %lld, %.3f s (induce %.3f, match %.3f, contract "
+                "%.3f, lanczos %.3f, sweep %.3f, fm %.3f, metrics %.3f), %.3f s -> results/%s.part.%d%s\n", r.k, o.ml_eps,
+                r.bisections, r.coarsest_fallbacks, r.infeasible_sweeps, (long long)r.total_weight, (long long)r.part_bound,
+                (long long)r.part_w_min, (long long)r.part_w_max, (long long)r.parts_over_bound, (long long)r.empty_parts,
+                (long long)r.cut_nets, (long long)r.connectivity, (long long)r.connectivity_w, (long long)r.soed,
+                (long long)r.levels_total, (long long)r.fm_moves, r.t_total, r.t_induce, r.t_match, r.t_contract,
+                r.t_lanczos, r.t_sweep, r.t_fm, r.t_metrics, secs(t0), base_name(o.input).c_str(), r.k,
+                o.ml_wlap ? ", wlap=1" : "");
     return 0;
 }
 
@@ -535,9 +574,15 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             else if (a == "--sweep-weighted") o.sweep_weighted = true;
             else if (a == "--no-kl") o.no_kl = true;
             else if (a == "--multilevel") {
+                if (o.kml) throw Fail{"--kway-multilevel stands in place of --multilevel"};
                 o.ml_eps = std::stod(need("--multilevel"));
                 o.ml = true;
                 if (!std::isfinite(o.ml_eps) || o.ml_eps < 0) throw Fail{"--multilevel takes an imbalance >= 0"};
+            } else if (a == "--kway-multilevel") {
+                if (o.ml && !o.kml) throw Fail{"--kway-multilevel stands in place of --multilevel"};
+                o.ml_eps = std::stod(need("--kway-multilevel"));
+                o.ml = o.kml = true;
+                if (!std::isfinite(o.ml_eps) || o.ml_eps < 0) throw Fail{"--kway-multilevel takes an imbalance >= 0"};
             } else if (a == "--ml-coarse") {
                 o.ml_coarse = std::stoi(need("--ml-coarse"));
                 o.ml_sub = true;
@@ -554,18 +599,18 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         } catch (const Fail& e) {
             std::fprintf(stderr, "Error: %s\n", e.msg.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
-            if (a.rfind("--m", 0) == 0) std::printf("%s", ML_USAGE);
+            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel") std::printf("%s", ML_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
-            if (a.rfind("--m", 0) == 0) std::printf("%s", ML_USAGE);
+            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel") std::printf("%s", ML_USAGE);
             return 1;
         }
     }
     try {
         if (o.ml || o.ml_sub) {
-            if (!o.ml || o.kway || o.refine || o.sweep || o.sweep_ratio || o.fm || o.weighted || o.sweep_weighted ||
+            if (!o.ml || (o.kml ? o.kway < 2 || o.kway > 256 : o.kway != 0) || o.refine || o.sweep || o.sweep_ratio || o.fm || o.weighted || o.sweep_weighted ||
                 o.no_kl || o.tool != "gKL2" || !(pos.size() == 2 && pos[1] == "-EIG")) {
                 std::printf("%s", ML_USAGE);
                 return 1;
@@ -573,7 +618,7 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             mkdirs();
             o.input = pos[0];
             o.eig = true;
-            return run_ml(o);
+            return o.kml ? run_kway_ml(o) : run_ml(o);
         }
         if ((o.sweep_weighted || o.no_kl) &&
             (!o.sweep_weighted || !o.sweep || !o.fm || !o.weighted || o.sweep_ratio || o.kway || o.tool != "gKL2" ||

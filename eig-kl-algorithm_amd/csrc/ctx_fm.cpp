@@ -30,7 +30,8 @@ void unpack_sides(const unsigned* side_w, int64_t n, uint8_t* side) {
 // The FM refinement on the device under either rule: D = FmDev with R =
 // ek_fm_result, or D = FmwDev with R = ek_fm_w_result and the weights in fi
 // (null otherwise: the unweighted run uploads none).  S: the sizes or weights
-// of the sides given; r.n and r.max_part are set.  Set-up: the counts and the
+// of the sides given, L: the sides' bounds (L_max twice, or the pair of §16, where
+// d is the slack difference |(S0 - L0) - (S1 - L1)|); r.n is set.  Set-up: the counts and the
 // cut (k_fm_counts).  A pass: the gains (k_fm_gains), the pass (k_fm_pass, one
 // workgroup, one launch), ONE 32-byte read of its record, then the rollback of
 // the moves past its best prefix (k_fm_rollback).  The move log, the sides and
@@ -41,7 +42,7 @@ void unpack_sides(const unsigned* side_w, int64_t n, uint8_t* side) {
 // the one pass the rule runs keeps nothing.
 template <class D, class R, class Final>
 void fm_device(const char* who, ek_ctx* c, const ek::RefineInput& in, const ek_fm_opts& o, const ek::FmwInput* fi,
-               const uint8_t* side, const int64_t S[2], clk::time_point t0, int64_t* pass_log, int64_t log_passes,
+               const uint8_t* side, const int64_t S[2], const int64_t L[2], clk::time_point t0, int64_t* pass_log, int64_t log_passes,
                ek_fm_move* move_log, int64_t move_cap, R& r, Final final) {
     constexpr bool WT = std::is_same_v<D, ek::dev::FmwDev>;
     constexpr int NCUT = WT ? 2 : 1;  // fm_counts' words of state, from state[3]
@@ -49,7 +50,7 @@ void fm_device(const char* who, ek_ctx* c, const ek::RefineInput& in, const ek_f
     if (nets == 0) {  // nothing can move, nothing is cut
         if (pass_log && log_passes > 0) {
             pass_log[0] = pass_log[1] = pass_log[2] = 0;
-            pass_log[3] = std::llabs(S[0] - S[1]);
+            pass_log[3] = std::llabs((S[0] - L[0]) - (S[1] - L[1]));
         }
         r.passes_run = 1;
         r.t_setup = since(t0);
@@ -97,9 +98,10 @@ void fm_device(const char* who, ek_ctx* c, const ek::RefineInput& in, const ek_f
     if constexpr (WT) {
         d.cw = d_cw.as<int32_t>();
         d.w = d_w.as<int32_t>();
-        d.lmax = r.max_part;
+        d.lmax = L[0];
+        d.lmax1 = L[1];
     } else {
-        d.lmax = int(std::min<int64_t>(r.max_part, INT32_MAX));
+        d.lmax = int(std::min<int64_t>(L[0], INT32_MAX));
     }
     d.net_ptr = d_ptr.as<int64_t>();
     d.inc_ptr = d_iptr.as<int64_t>();
@@ -137,8 +139,8 @@ void fm_device(const char* who, ek_ctx* c, const ek::RefineInput& in, const ek_f
     r.t_setup = since(t0);
 
     const auto tp = clk::now();
-    const char* dname = WT ? "|S0 - S1|" : "|s0 - s1|";
-    int64_t cut = r.cut_before, dist = std::llabs(S[0] - S[1]);
+    const char* dname = WT ? (L[0] == L[1] ? "|S0 - S1|" : "slack difference") : "|s0 - s1|";
+    int64_t cut = r.cut_before, dist = std::llabs((S[0] - L[0]) - (S[1] - L[1]));
     for (;;) {
         if (o.max_passes > 0 && r.passes >= o.max_passes) break;
         ek::dev::fm_gains(s, d);
@@ -183,6 +185,40 @@ void fm_device(const char* who, ek_ctx* c, const ek::RefineInput& in, const ek_f
     r.t_metrics = since(tm);
 }
 
+// The weighted refinement on the device under the sides' bounds L, R =
+// ek_fm_w_result or ek_fm_wb_result with n, W and its bound fields set; the
+// sides read back are measured again on the host and held against the device's
+// weights and its last d.
+template <class R>
+void fmw_device(const char* who, ek_ctx* c, const ek_hgr* h, const ek::FmwInput& fi, const int64_t L[2],
+                clk::time_point t0, uint8_t* side, int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log,
+                int64_t move_cap, R& r) {
+    const int64_t n = h->nodes;
+    int64_t S[2], size[2];
+    auto measure = [&] {  // the sides' weights and node counts from side[]
+        S[0] = S[1] = size[0] = size[1] = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            S[side[i]] += fi.w[size_t(i)];
+            ++size[side[i]];
+        }
+        r.w0 = S[0];
+        r.w1 = S[1];
+        r.n0 = size[0];
+        r.n1 = size[1];
+    };
+    measure();
+    fm_device<ek::dev::FmwDev>(who, c, fi.in, fi.opts, &fi, side, S, L, t0, pass_log, log_passes, move_log, move_cap, r,
+                               [&](const FmEnd& e) {
+        unpack_sides(e.side_w, n, side);
+        measure();  // again from the sides read back, against the device's
+        if (r.cut != e.cut || e.state[0] != e.cut || e.state[1] != S[0] || e.state[2] != S[1] ||
+            std::llabs((S[0] - L[0]) - (S[1] - L[1])) != e.dist)
+            ek::fail(EK_EHIP, "%s: the passes left a cut of %lld and weights %lld | %lld, the sides count %lld and %lld | "
+                     "%lld", who, (long long)e.cut, e.state[1], e.state[2], (long long)r.cut, (long long)S[0],
+                     (long long)S[1]);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -203,7 +239,8 @@ int ek_fm_refine(ek_ctx* c, const ek_hgr* h, const ek_fm_opts* opts, uint8_t* si
     for (int64_t i = 0; i < n; ++i) ++size[side[i]];
     r.n0 = size[0];
     r.n1 = size[1];
-    fm_device<ek::dev::FmDev>("ek_fm_refine", c, in, o, nullptr, side, size, t0, pass_log, log_passes, move_log, move_cap,
+    const int64_t L[2] = {r.max_part, r.max_part};
+    fm_device<ek::dev::FmDev>("ek_fm_refine", c, in, o, nullptr, side, size, L, t0, pass_log, log_passes, move_log, move_cap,
                               r, [&](const FmEnd& e) {
         if (r.cut != e.cut || e.state[0] != e.cut || e.state[1] + e.state[2] != n)
             ek::fail(EK_EHIP, "ek_fm_refine: the passes left a cut of %lld, the sides' nets count %lld (sizes %lld + %lld of "
@@ -224,34 +261,31 @@ int ek_fm_refine_w(ek_ctx* c, const ek_hgr* h, const ek_fm_opts* opts, uint8_t* 
     fm_check_ctx("ek_fm_refine_w", c);
     ek::FmwInput fi;
     ek::fmw_prepare("ek_fm_refine_w", h, opts, side, fi);
-    const int64_t n = h->nodes;
     ek_fm_w_result r{};
-    r.n = n;
+    r.n = h->nodes;
     r.total_weight = fi.total;
     r.max_part = fi.max_part;
-    int64_t S[2], size[2];
-    auto measure = [&] {  // the sides' weights and node counts from side[]
-        S[0] = S[1] = size[0] = size[1] = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            S[side[i]] += fi.w[size_t(i)];
-            ++size[side[i]];
-        }
-        r.w0 = S[0];
-        r.w1 = S[1];
-        r.n0 = size[0];
-        r.n1 = size[1];
-    };
-    measure();
-    fm_device<ek::dev::FmwDev>("ek_fm_refine_w", c, fi.in, fi.opts, &fi, side, S, t0, pass_log, log_passes, move_log,
-                               move_cap, r, [&](const FmEnd& e) {
-        unpack_sides(e.side_w, n, side);
-        measure();  // again from the sides read back, against the device's
-        if (r.cut != e.cut || e.state[0] != e.cut || e.state[1] != S[0] || e.state[2] != S[1] ||
-            std::llabs(S[0] - S[1]) != e.dist)
-            ek::fail(EK_EHIP, "ek_fm_refine_w: the passes left a cut of %lld and weights %lld | %lld, the sides count %lld "
-                     "and %lld | %lld", (long long)e.cut, e.state[1], e.state[2], (long long)r.cut, (long long)S[0],
-                     (long long)S[1]);
-    });
+    const int64_t L[2] = {fi.max_part, fi.max_part};
+    fmw_device("ek_fm_refine_w", c, h, fi, L, t0, side, pass_log, log_passes, move_log, move_cap, r);
+    if (result) *result = r;
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_fm_refine_wb(ek_ctx* c, const ek_hgr* h, const ek_fm_opts* opts, const int64_t bounds[2], uint8_t* side,
+                    int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap,
+                    ek_fm_wb_result* result) {
+    EK_TRY
+    const auto t0 = clk::now();
+    fm_check_ctx("ek_fm_refine_wb", c);
+    ek::FmwInput fi;
+    ek::fmwb_prepare("ek_fm_refine_wb", h, opts, bounds, side, fi);
+    ek_fm_wb_result r{};
+    r.n = h->nodes;
+    r.total_weight = fi.total;
+    r.bound0 = bounds[0];
+    r.bound1 = bounds[1];
+    fmw_device("ek_fm_refine_wb", c, h, fi, bounds, t0, side, pass_log, log_passes, move_log, move_cap, r);
     if (result) *result = r;
     return EK_OK;
     EK_CATCH

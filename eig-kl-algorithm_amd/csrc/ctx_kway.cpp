@@ -46,6 +46,47 @@ int ek_kway_metrics(ek_ctx* c, int64_t nets, const int64_t* net_ptr, const int32
     EK_CATCH
 }
 
+// The weighted metrics on the device: two launches (the nets, the nodes) into
+// one record of 4 + 256 int64 words, read once.  Every buffer is local to the
+// call.
+int ek_kway_metrics_w(ek_ctx* c, const ek_hgr* h, const int32_t* part, int32_t k, int64_t* out) {
+    EK_TRY
+    check_ctx(c);
+    if (!h || !out || k < 1 || k > 256 || (h->nodes > 0 && !part)) ek::fail(EK_EINVAL, "ek_kway_metrics_w: bad argument");
+    const int64_t n = h->nodes, nets = h->nets;
+    if (n > INT32_MAX - 1) ek::fail(EK_EINVAL, "ek_kway_metrics_w: %lld nodes", (long long)n);
+    if ((!h->node_w.empty() && int64_t(h->node_w.size()) != n) || (!h->net_w.empty() && int64_t(h->net_w.size()) != nets))
+        ek::fail(EK_EINVAL, "ek_kway_metrics_w: weight arrays of the wrong length");
+    std::vector<uint8_t> part8(static_cast<size_t>(n));
+    for (int64_t i = 0; i < n; ++i) {
+        if (part[i] < 0 || part[i] >= k)
+            ek::fail(EK_EINVAL, "ek_kway_metrics_w: part %d of node %lld outside [0, %d)", part[i], (long long)i, k);
+        part8[size_t(i)] = uint8_t(part[i]);
+    }
+    std::fill(out, out + 4 + k, int64_t(0));
+    if (n == 0) return EK_OK;
+    const int64_t npins = nets > 0 ? h->net_ptr[size_t(nets)] : 0;
+    hipStream_t s = c->stream;
+    constexpr size_t WORDS = 4 + 256;
+    DBuf d_ptr, d_pins, d_cw, d_w, d_part, d_out;
+    if (nets > 0) upload(d_ptr, h->net_ptr.data(), size_t(nets) + 1, s);
+    if (npins > 0) upload(d_pins, h->pins.data(), size_t(npins), s);
+    if (nets > 0 && !h->net_w.empty()) upload(d_cw, h->net_w.data(), size_t(nets), s);
+    if (!h->node_w.empty()) upload(d_w, h->node_w.data(), size_t(n), s);
+    upload(d_part, part8.data(), size_t(n), s);
+    d_out.ensure(WORDS * sizeof(unsigned long long));
+    HIPCHK(hipMemsetAsync(d_out.p, 0, WORDS * sizeof(unsigned long long), s));
+    ek::dev::kway_metrics_w(s, npins > 0 ? nets : 0, d_ptr.as<int64_t>(), d_pins.as<int32_t>(), d_cw.as<int32_t>(), n,
+                            d_part.as<uint8_t>(), d_w.as<int32_t>(), d_out.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    long long got[WORDS];
+    HIPCHK(hipMemcpyAsync(got, d_out.p, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int j = 0; j < 4 + k; ++j) out[j] = got[j];
+    return EK_OK;
+    EK_CATCH
+}
+
 // The k-way refinement on the device (kernels_refine.hip): six launches a
 // round, then ONE 8-byte read (the round's accepted moves) to learn whether to
 // go on.  The rounds' four counters stay in a device log of RF_LOG rounds,

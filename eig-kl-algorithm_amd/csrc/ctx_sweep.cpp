@@ -147,13 +147,15 @@ void sweep_on_device(ek_ctx* c, const ek_hgr* h, const double* v, const ek_sweep
     if (result) *result = r;
 }
 
-// The weighted sweep cut of v (device, n doubles) over h's nets and weights;
-// r comes from sweepw_check (n, W, L_max).  Every buffer is local to the call.
+// The weighted sweep cut of v (device, n doubles) over h's nets and weights
+// under the sides' bounds l0, l1; r comes from sweepw_check (n, W, L_max = l0 =
+// l1) or sweepwb_check (n, W, L0, L1).  Every buffer is local to the call.
 // Host synchronisations: the sort's two, one after the profiles and P (for
 // their time), one for the 80-byte result record; order, profile_w and P are
 // read only when asked for.
-void sweepw_on_device(ek_ctx* c, const ek_hgr* h, const double* v, ek_sweep_w_result r, int32_t* order_out,
-                      int64_t* profile_out, int64_t* prefix_out, ek_sweep_w_result* result) {
+template <class R>
+void sweepw_on_device(ek_ctx* c, const ek_hgr* h, const double* v, R r, int64_t l0, int64_t l1, int32_t* order_out,
+                      int64_t* profile_out, int64_t* prefix_out, R* result) {
     hipStream_t s = c->stream;
     const int64_t n = h->nodes;
     const int ni = int(n);
@@ -185,7 +187,7 @@ void sweepw_on_device(ek_ctx* c, const ek_hgr* h, const double* v, ek_sweep_w_re
     part.ensure(size_t(5) * size_t(ek::dev::sweepw_select_blocks(ni)) * sizeof(u64));
     rec.ensure(ek::dev::SWEEPW_REC * sizeof(long long));
     ek::dev::sweepw_select(s, pf.profw.as<u64>(), prefix.as<u64>(), pf.prof.as<unsigned>(), ni, u64(r.total_weight),
-                           u64(r.max_part), part.as<u64>(), pf.span.as<unsigned>(), pf.nspan, rec.as<long long>());
+                           u64(l0), u64(l1), part.as<u64>(), pf.span.as<unsigned>(), pf.nspan, rec.as<long long>());
     HIPCHK(hipGetLastError());
     long long out[ek::dev::SWEEPW_REC] = {-1};
     HIPCHK(hipMemcpyAsync(out, rec.p, sizeof out, hipMemcpyDeviceToHost, s));
@@ -263,7 +265,20 @@ int ek_sweep_cut_w(ek_ctx* c, const ek_hgr* h, const double* v_host, const ek_sw
     ek::sweepw_check("ek_sweep_cut_w", h, v_host, opts, r);
     DBuf v;
     upload(v, v_host, size_t(h->nodes), c->stream);
-    sweepw_on_device(c, h, v.as<double>(), r, order_out, profile_out, prefix_out, result);
+    sweepw_on_device(c, h, v.as<double>(), r, r.max_part, r.max_part, order_out, profile_out, prefix_out, result);
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_sweep_cut_wb(ek_ctx* c, const ek_hgr* h, const double* v_host, const ek_sweep_opts* opts, const int64_t bounds[2],
+                    int32_t* order_out, int64_t* profile_out, int64_t* prefix_out, ek_sweep_wb_result* result) {
+    EK_TRY
+    check_ctx(c);
+    ek_sweep_wb_result r{};
+    ek::sweepwb_check("ek_sweep_cut_wb", h, v_host, opts, bounds, r);
+    DBuf v;
+    upload(v, v_host, size_t(h->nodes), c->stream);
+    sweepw_on_device(c, h, v.as<double>(), r, r.bound0, r.bound1, order_out, profile_out, prefix_out, result);
     return EK_OK;
     EK_CATCH
 }
@@ -287,7 +302,7 @@ int ek_kl_set_partition_fiedler_sweep_w(ek_ctx* c, const ek_hgr* h, const ek_swe
     const double* v = sweep_split_vector("ek_kl_set_partition_fiedler_sweep_w", c, h);
     ek_sweep_w_result r{};
     ek::sweepw_check("ek_kl_set_partition_fiedler_sweep_w", h, v, opts, r);
-    sweepw_on_device(c, h, v, r, nullptr, nullptr, nullptr, &r);
+    sweepw_on_device(c, h, v, r, r.max_part, r.max_part, nullptr, nullptr, nullptr, &r);
     const int rc = sweep_split_at(c, "weighted sweep split", r.n1);
     if (rc != EK_OK) return rc;
     if (result) *result = r;

@@ -211,6 +211,13 @@ ek_sweep_opts sweep_check(const char* who, const ek_hgr* h, const double* v, con
 void sweep_window(int64_t n, double imbalance, ek_sweep_result& r);
 ek_sweep_opts sweepw_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts,
                            ek_sweep_w_result& r);
+// The per-side bounds of §16 (the bounded sweep, FM and V-cycle share it):
+// W <= 2^61, 0 <= bounds[s] <= W, bounds[0] + bounds[1] >= W, EK_EINVAL otherwise
+void bounds_check(const char* who, int64_t W, const int64_t bounds[2]);
+// the bounded sweep: sweepw_check with the imbalance ignored, bounds_check, and
+// n, W, L0, L1 of the result
+ek_sweep_opts sweepwb_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts,
+                            const int64_t bounds[2], ek_sweep_wb_result& r);
 
 // fm.cpp — what the host and the device FM refinement share besides
 // refine_max_part and refine_prepare: the argument checks (EK_EINVAL as
@@ -230,6 +237,10 @@ struct FmwInput : WeightedInput {
     ek_fm_opts opts;
 };
 void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const uint8_t* side, FmwInput& out);
+// the bounded entries' (§16): the same with the imbalance ignored and
+// bounds_check in place of L_max (max_part = the greater bound)
+void fmwb_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const int64_t bounds[2], const uint8_t* side,
+                  FmwInput& out);
 // the part of it that needs no sides (the matching shares it): refine_prepare,
 // cw, w and the range rules; returns W
 int64_t weights_prepare(const char* who, const ek_hgr* h, WeightedInput& out);
@@ -774,6 +785,12 @@ int kway_metrics_blocks(int64_t nets);
 void kway_metrics(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* part,
                   unsigned* out);
 
+// the weighted metrics (ek_kway_metrics_w) into out (4 + 256 words, zero
+// before): cut nets, connectivity, weighted connectivity (cw: c(e) per net,
+// null: 1), SOED, then the weight of each part over the n nodes (w null: 1)
+void kway_metrics_w(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* cw,
+                    int64_t n, const uint8_t* part, const int32_t* w, unsigned long long* out);
+
 // kernels_refine.hip — one round of the k-way refinement (ek_kway_refine)
 struct RefineDev {
     int n, nets, k, lmax;
@@ -827,13 +844,15 @@ void sweep_select(hipStream_t s, const unsigned* profile, int n, int64_t s_lo, i
 // pw[0] = 0, pw[r + 1] = w[order[r]] (w null: 1): its inclusive scan is P
 void sweepw_gather(hipStream_t s, const int32_t* order, const int32_t* w, int n, unsigned long long* pw);
 // the weighted sweep's choice over s = 1 .. n - 1 from profile_w and P (n + 1
-// words each), W and L_max; part: 5 * sweepw_select_blocks(n) words.
+// words each), W and the sides' bounds (side 0, side 1; §13: both L_max);
+// part: 5 * sweepw_select_blocks(n) words.
 // rec[0..9] = s* (-1: none), feasible, s_lo, s_hi, profile_w[s*], profile[s*],
 // profile_w[n / 2], the sum of span_part[0:nspan), P[s*], P[n]
 int sweepw_select_blocks(int n);
 void sweepw_select(hipStream_t s, const unsigned long long* profw, const unsigned long long* prefix,
-                   const unsigned* profile, int n, unsigned long long total, unsigned long long max_part,
-                   unsigned long long* part, const unsigned* span_part, int nspan, long long* rec);
+                   const unsigned* profile, int n, unsigned long long total, unsigned long long bound0,
+                   unsigned long long bound1, unsigned long long* part, const unsigned* span_part, int nspan,
+                   long long* rec);
 
 // kernels_fm.hip — the FM refinement of a bipartition, unweighted (FmDev,
 // ek_fm_refine) and weighted (FmwDev, ek_fm_refine_w): one set of kernels,
@@ -862,6 +881,7 @@ struct FmDev {
 struct FmwDev : FmDev {
     const int32_t *cw, *w;  // c(e) per net, w(v) per node
     long long lmax;         // the 64-bit L_max: hides FmDev's, so d.lmax is the bound of either rule
+    long long lmax1;        // side 1's bound; lmax is then side 0's (§16).  §12: lmax1 = lmax
 };
 // D is FmDev or FmwDev in all four.
 // cnt(e, .) of the side bitmap, and state[3] (zero before) += the cut nets;

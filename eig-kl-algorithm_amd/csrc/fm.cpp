@@ -45,17 +45,23 @@ struct FmPasses {
 // Steps 1-5 of the rule, pass after pass, on side[] from the cut `cut`.  WT =
 // false is the unweighted rule (cw and w are not read: every c(e) and w(v) is
 // 1), WT = true the weighted one with c(e) = cw[e] per participating net and
-// w(v) = w[v].  Everything the loop changes but side[] and the logs is a local
+// w(v) = w[v].  L[s] is the most side s may hold: L_max twice under §11 and
+// §12, the per-side bounds of §16 otherwise, where the balance key is the slack
+// difference |(S0 - L[0]) - (S1 - L[1])| and equal gains go to the side of less
+// slack; with L[0] = L[1] both are §12's (|S0 - S1|, the heavier side).
+// Everything the loop changes but side[] and the logs is a local
 // of this frame, returned by value, and the input arrays are reached through
 // local pointers: side[] is of a character type, so a store to it could alias
 // whatever is read through a reference, which would then be read again.
 template <bool WT>
 FmPasses fm_host_passes(const char* who, const ek::RefineInput& in, const ek_fm_opts& o, const int32_t* cw,
-                        const int32_t* w, int64_t n, int64_t max_part, int64_t cut, uint8_t* side, int64_t* pass_log,
+                        const int32_t* w, int64_t n, const int64_t* bounds, int64_t cut, uint8_t* side, int64_t* pass_log,
                         int64_t log_passes, ek_fm_move* move_log, int64_t move_cap) {
     const auto tp = clk::now();
     FmPasses r;
     int64_t S[2] = {0, 0};
+    const int64_t L[2] = {bounds[0], bounds[1]};
+    auto slack_diff = [&S, &L] { return std::llabs((S[0] - L[0]) - (S[1] - L[1])); };
     auto w_of = [w](int32_t v) -> int64_t {
         if constexpr (WT) return w[size_t(v)];
         else return 1;
@@ -110,7 +116,7 @@ FmPasses fm_host_passes(const char* who, const ek::RefineInput& in, const ek_fm_
             free_[side[v]].insert({-gain[size_t(v)], int32_t(v)});
         }
         moved.clear();
-        int64_t t = 0, t_best = 0, c_best = cut, d_best = std::llabs(S[0] - S[1]);
+        int64_t t = 0, t_best = 0, c_best = cut, d_best = slack_diff();
         for (;;) {
             // 2. the candidates: a side's top node, when the other side has room for it (only the top is tried;
             // unweighted, that is while the other side has room)
@@ -119,10 +125,11 @@ FmPasses fm_host_passes(const char* who, const ek::RefineInput& in, const ek_fm_
             for (int a = 0; a < 2; ++a) {
                 if (free_[a].empty()) continue;
                 k[a] = *free_[a].begin();
-                if (S[1 - a] + w_of(k[a].second) > max_part) continue;
+                if (S[1 - a] + w_of(k[a].second) > L[1 - a]) continue;
                 if (pick < 0) pick = a;
                 else if (k[a].first != k[pick].first) pick = k[a].first < k[pick].first ? a : pick;  // the greater g
-                else if (S[a] != S[pick]) pick = S[a] > S[pick] ? a : pick;  // the side holding more / the heavier
+                else if (S[a] - L[a] != S[pick] - L[pick])  // the side of less slack (one bound: holding more / the heavier)
+                    pick = S[a] - L[a] > S[pick] - L[pick] ? a : pick;
                 else pick = k[a].second < k[pick].second ? a : pick;         // the smaller id
             }
             if (pick < 0) break;
@@ -135,7 +142,7 @@ FmPasses fm_host_passes(const char* who, const ek::RefineInput& in, const ek_fm_
             moved.push_back(v);
             ++t;
             cut -= g;
-            const int64_t d = std::llabs(S[0] - S[1]);
+            const int64_t d = slack_diff();
             if (r.moves_tried < move_cap && move_log) move_log[r.moves_tried] = ek_fm_move{v, int32_t(g), cut};
             ++r.moves_tried;
             if (cut < c_best || (cut == c_best && d < d_best)) {
@@ -191,6 +198,36 @@ void fm_host_counters(const FmPasses& p, R& r) {
     r.moves_tried = p.moves_tried;
     r.moves_kept = p.moves_kept;
     r.t_passes = p.t_passes;
+}
+
+// The weighted checker under the sides' bounds L (§12: L_max twice; §16: L0, L1),
+// R = ek_fm_w_result or ek_fm_wb_result with n, W and its bound fields set: the
+// cut before and after counted by ek_bipart_metrics_host, the passes between.
+template <class R>
+void fmw_host_run(const char* who, const ek_hgr* h, const ek::FmwInput& fi, const int64_t* L, clk::time_point t0,
+                  uint8_t* side, int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, R& r) {
+    const int64_t n = h->nodes;
+    int64_t m[4];
+    chk(ek_bipart_metrics_host(h, side, m));
+    r.cut_before = m[0];
+    r.cut_nets_before = m[1];
+    r.t_setup = since(t0);
+
+    const FmPasses p = fm_host_passes<true>(who, fi.in, fi.opts, fi.cw.data(), fi.w.data(), n, L, r.cut_before, side,
+                                            pass_log, log_passes, move_log, move_cap);
+    fm_host_counters(p, r);
+
+    const auto tm = clk::now();
+    chk(ek_bipart_metrics_host(h, side, m));
+    r.cut = m[0];
+    r.cut_nets = m[1];
+    r.w0 = m[2];
+    r.w1 = m[3];
+    for (int64_t v = 0; v < n; ++v) ++(side[v] ? r.n1 : r.n0);
+    if (r.cut != p.cut || r.w0 != p.S[0] || r.w1 != p.S[1])
+        ek::fail(EK_EINVAL, "%s: tracked cut %lld and weights %lld | %lld, counted %lld and %lld | %lld", who,
+                 (long long)p.cut, (long long)p.S[0], (long long)p.S[1], (long long)r.cut, (long long)r.w0, (long long)r.w1);
+    r.t_metrics = since(tm);
 }
 }  // namespace
 
@@ -335,8 +372,9 @@ int ek_fm_refine_host(const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side, in
     r.cut_before = m[0];
     r.t_setup = since(t0);
 
-    const FmPasses p = fm_host_passes<false>("ek_fm_refine_host", in, o, nullptr, nullptr, n, r.max_part, r.cut_before, side,
-                                             pass_log, log_passes, move_log, move_cap);
+    const int64_t L[2] = {r.max_part, r.max_part};
+    const FmPasses p = fm_host_passes<false>("ek_fm_refine_host", in, o, nullptr, nullptr, n, L, r.cut_before, side, pass_log,
+                                             log_passes, move_log, move_cap);
     fm_host_counters(p, r);
 
     const auto tm = clk::now();
@@ -360,32 +398,29 @@ int ek_fm_refine_w_host(const ek_hgr* h, const ek_fm_opts* opts, uint8_t* side, 
     const auto t0 = clk::now();
     ek::FmwInput fi;
     ek::fmw_prepare("ek_fm_refine_w_host", h, opts, side, fi);
-    const int64_t n = h->nodes;
     ek_fm_w_result r{};
-    r.n = n;
+    r.n = h->nodes;
     r.total_weight = fi.total;
     r.max_part = fi.max_part;
-    int64_t m[4];
-    chk(ek_bipart_metrics_host(h, side, m));
-    r.cut_before = m[0];
-    r.cut_nets_before = m[1];
-    r.t_setup = since(t0);
+    const int64_t L[2] = {fi.max_part, fi.max_part};
+    fmw_host_run("ek_fm_refine_w_host", h, fi, L, t0, side, pass_log, log_passes, move_log, move_cap, r);
+    if (result) *result = r;
+    return EK_OK;
+    EK_CATCH
+}
 
-    const FmPasses p = fm_host_passes<true>("ek_fm_refine_w_host", fi.in, fi.opts, fi.cw.data(), fi.w.data(), n, r.max_part,
-                                            r.cut_before, side, pass_log, log_passes, move_log, move_cap);
-    fm_host_counters(p, r);
-
-    const auto tm = clk::now();
-    chk(ek_bipart_metrics_host(h, side, m));
-    r.cut = m[0];
-    r.cut_nets = m[1];
-    r.w0 = m[2];
-    r.w1 = m[3];
-    for (int64_t v = 0; v < n; ++v) ++(side[v] ? r.n1 : r.n0);
-    if (r.cut != p.cut || r.w0 != p.S[0] || r.w1 != p.S[1])
-        ek::fail(EK_EINVAL, "ek_fm_refine_w_host: tracked cut %lld and weights %lld | %lld, counted %lld and %lld | %lld",
-                 (long long)p.cut, (long long)p.S[0], (long long)p.S[1], (long long)r.cut, (long long)r.w0, (long long)r.w1);
-    r.t_metrics = since(tm);
+int ek_fm_refine_wb_host(const ek_hgr* h, const ek_fm_opts* opts, const int64_t bounds[2], uint8_t* side, int64_t* pass_log,
+                         int64_t log_passes, ek_fm_move* move_log, int64_t move_cap, ek_fm_wb_result* result) {
+    EK_TRY
+    const auto t0 = clk::now();
+    ek::FmwInput fi;
+    ek::fmwb_prepare("ek_fm_refine_wb_host", h, opts, bounds, side, fi);
+    ek_fm_wb_result r{};
+    r.n = h->nodes;
+    r.total_weight = fi.total;
+    r.bound0 = bounds[0];
+    r.bound1 = bounds[1];
+    fmw_host_run("ek_fm_refine_wb_host", h, fi, bounds, t0, side, pass_log, log_passes, move_log, move_cap, r);
     if (result) *result = r;
     return EK_OK;
     EK_CATCH

@@ -67,6 +67,19 @@ void fmw_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const
     out.max_part = refine_max_part(out.total, 2, out.opts.imbalance);
 }
 
+void fmwb_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, const int64_t bounds[2], const uint8_t* side,
+                  FmwInput& out) {
+    ek_fm_opts o;
+    ek_fm_default_opts(&o);
+    if (opts) o = *opts;
+    o.imbalance = 0.0;  // ignored: the bounds stand in its place
+    if (!bounds) fail(EK_EINVAL, "%s: null bounds", who);
+    out.opts = fm_check(who, h, &o, side);
+    out.total = weights_prepare(who, h, out);
+    bounds_check(who, out.total, bounds);
+    out.max_part = std::max(bounds[0], bounds[1]);
+}
+
 }  // namespace ek
 
 extern "C" {

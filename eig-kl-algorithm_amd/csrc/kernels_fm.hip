@@ -290,7 +290,18 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_pass(D d, int stall, long lon
 
     long long cut = d.state[0];
     S s0 = S(d.state[1]), s1 = S(d.state[2]);
-    auto dist = [](S x, S y) { return x > y ? x - y : y - x; };
+    // weighted: the sides' bounds L0 = d.lmax, L1 = d.lmax1 (§12: equal; §16: a pair), the slack S_a - L_a of a
+    // side, and d = |slack 0 - slack 1|; with L0 = L1 these are L_max, the order of the weights and |S0 - S1|
+    [[maybe_unused]] S skew = 0;
+    if constexpr (WT) skew = d.lmax - d.lmax1;
+    auto dist = [&](S x, S y) {
+        if constexpr (WT) {
+            const S z = x - y - skew;
+            return z < 0 ? -z : z;
+        } else {
+            return x > y ? x - y : y - x;
+        }
+    };
     long long c_best = cut;
     S d_best = dist(s0, s1);
     [[maybe_unused]] S s0_best = s0;
@@ -329,11 +340,15 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_pass(D d, int stall, long lon
             w0 = m0 != 0ull ? d.w[v0] : 0;
             w1 = m1 != 0ull ? d.w[v1] : 0;
         }
-        const bool have0 = s1 + w0 <= d.lmax && m0 != 0ull, have1 = s0 + w1 <= d.lmax && m1 != 0ull;
+        S into1 = d.lmax;  // the bound of the side that side 0's top node would enter; into0: side 1's
+        if constexpr (WT) into1 = d.lmax1;
+        const S into0 = d.lmax;
+        const bool have0 = s1 + w0 <= into1 && m0 != 0ull, have1 = s0 + w1 <= into0 && m1 != 0ull;
         if (!have0 && !have1) break;
         const int g0 = int(unsigned(m0 >> 32) - 0x80000000u), g1 = int(unsigned(m1 >> 32) - 0x80000000u);
+        const S k0 = s0 - skew, k1 = s1;  // (the slacks, both shifted by L1: their order is the slacks')
         unsigned a;  // the side the node leaves
-        if (have0 && have1) a = g0 != g1 ? unsigned(g1 > g0) : s0 != s1 ? unsigned(s1 > s0) : unsigned(v1 < v0);
+        if (have0 && have1) a = g0 != g1 ? unsigned(g1 > g0) : k0 != k1 ? unsigned(k1 > k0) : unsigned(v1 < v0);
         else a = have1 ? 1u : 0u;
         const unsigned v = a ? v1 : v0;
         const int g = a ? g1 : g0;

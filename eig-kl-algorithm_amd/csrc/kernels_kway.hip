@@ -272,7 +272,106 @@ __global__ __launch_bounds__(KM_THREADS) void k_kway_metrics(long long nets, con
     }
 }
 
+// The weighted sibling (ek_kway_metrics_w): the same walk over the nets, with
+// c(e) (cw null: 1) in a fourth sum, the weighted connectivity sum c(e)
+// (lambda_e - 1).  Every sum is 64-bit, reduced over the wave and the workgroup
+// and added to out[0..3] (zero before) with one integer atomic each per
+// workgroup that has something to add: integer adds commute, so the totals do
+// not depend on the order the workgroups arrive in.
+__global__ __launch_bounds__(KM_THREADS) void k_kway_metrics_w(long long nets, const int64_t* __restrict__ net_ptr,
+                                                               const int32_t* __restrict__ pins,
+                                                               const int32_t* __restrict__ cw,
+                                                               const uint8_t* __restrict__ part,
+                                                               u64* __restrict__ out) {
+    __shared__ u64 ws[4][KM_THREADS / 64];
+    const int t = threadIdx.x, l = t & 63;
+    const long long e = blockIdx.x * (long long)KM_THREADS + t;
+    u64 cut = 0, conn = 0, connw = 0, soed = 0;  // this thread's nets (lane 0: also the wave's long nets)
+    auto add = [&](unsigned lambda, long long net) {
+        if (lambda >= 2u) {
+            cut += 1ull;
+            conn += lambda - 1u;
+            connw += u64(cw ? cw[net] : 1) * (lambda - 1u);
+            soed += lambda;
+        }
+    };
+    int64_t p0 = 0, p1 = 0;
+    if (e < nets) {
+        p0 = net_ptr[e];
+        p1 = net_ptr[e + 1];
+    }
+    const bool is_long = p1 - p0 > KM_SHORT;
+    if (p1 - p0 >= 2 && !is_long) {
+        PartMask m;
+        for (int64_t p = p0; p < p1; ++p) m.set(part[pins[p]]);
+        add(m.count(), e);
+    }
+    // the wave's long nets, one after the other (the ballot is wave-uniform)
+    u64 todo = __ballot(is_long);
+    while (todo) {
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1ull;
+        const int64_t q0 = __shfl(p0, src, 64), q1 = __shfl(p1, src, 64);
+        PartMask m;
+        for (int64_t p = q0 + l; p < q1; p += 64) m.set(part[pins[p]]);
+        for (int o = 32; o > 0; o >>= 1) {
+            m.m0 |= __shfl_xor(m.m0, o, 64);
+            m.m1 |= __shfl_xor(m.m1, o, 64);
+            m.m2 |= __shfl_xor(m.m2, o, 64);
+            m.m3 |= __shfl_xor(m.m3, o, 64);
+        }
+        if (l == 0) add(m.count(), e - l + src);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cut += __shfl_xor(cut, o, 64);
+        conn += __shfl_xor(conn, o, 64);
+        connw += __shfl_xor(connw, o, 64);
+        soed += __shfl_xor(soed, o, 64);
+    }
+    if (l == 0) {
+        ws[0][t >> 6] = cut;
+        ws[1][t >> 6] = conn;
+        ws[2][t >> 6] = connw;
+        ws[3][t >> 6] = soed;
+    }
+    __syncthreads();
+    if (t < 4) {
+        const u64* c = ws[t];
+        const u64 sum = c[0] + c[1] + c[2] + c[3];
+        if (sum) atomicAdd(out + t, sum);
+    }
+}
+
+// out[p] (256 words, zero before) += the weight of the nodes of part p (w null:
+// 1 a node): a workgroup sums its nodes into 256 LDS words, then adds the
+// non-zero ones to out.  Integer atomics only.
+__global__ __launch_bounds__(KM_THREADS) void k_kway_part_weights(long long n, const uint8_t* __restrict__ part,
+                                                                  const int32_t* __restrict__ w, u64* __restrict__ out) {
+    __shared__ u64 acc[256];
+    const int t = threadIdx.x;
+    static_assert(KM_THREADS == 256, "one LDS word a thread");
+    acc[t] = 0ull;
+    __syncthreads();
+    const long long v = blockIdx.x * (long long)KM_THREADS + t;
+    if (v < n) {
+        const u64 x = w ? u64(w[v]) : 1ull;
+        if (x) atomicAdd(&acc[part[v]], x);
+    }
+    __syncthreads();
+    if (acc[t]) atomicAdd(out + t, acc[t]);
+}
+
 int kway_metrics_blocks(int64_t nets) { return int((nets + KM_THREADS - 1) / KM_THREADS); }
+
+void kway_metrics_w(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const int32_t* cw,
+                    int64_t n, const uint8_t* part, const int32_t* w, u64* out) {
+    if (nets > 0)
+        hipLaunchKernelGGL(k_kway_metrics_w, dim3(unsigned(kway_metrics_blocks(nets))), dim3(KM_THREADS), 0, s,
+                           (long long)nets, net_ptr, pins, cw, part, out);
+    if (n > 0)
+        hipLaunchKernelGGL(k_kway_part_weights, dim3(unsigned((n + KM_THREADS - 1) / KM_THREADS)), dim3(KM_THREADS), 0, s,
+                           (long long)n, part, w, out + 4);
+}
 
 void kway_metrics(hipStream_t s, int64_t nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* part,
                   unsigned* out) {

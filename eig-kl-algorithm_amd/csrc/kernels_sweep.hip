@@ -471,11 +471,15 @@ __global__ __launch_bounds__(SL_THREADS) void k_sweep_finish(const unsigned* __r
 // ---------------------------------------------------------------------------
 // The weighted sweep's choice: one reduction over the splits s = 1 .. n - 1.
 // A split's key is
-//   feasible:    (profile_w[s],          |2 P[s] - W|, s)
-//   infeasible:  (2^63 + |2 P[s] - W|,   profile_w[s], s)
+//   feasible:    (profile_w[s],   D[s], s)
+//   infeasible:  (2^63 + D[s],    profile_w[s], s)
+// with D[s] = |2 P[s] - W + (L0 - L1)|, the slack difference under the per-side
+// bounds (L0, L1) of §16 (feasible: P[s] <= L1 and W - P[s] <= L0); §13's one
+// bound is L0 = L1 = L_max, where D[s] = |2 P[s] - W|.  The keys are
 // compared lexicographically: a strict total order (every tie ends in s) that
 // places every feasible split before every infeasible one (profile_w <= 2^62
-// and |2 P - W| <= W <= 2^62 leave bit 63 free), so the least key is the
+// and D <= 2^62 leave bit 63 free: D <= W <= 2^62 under one bound, D <= 2 W <=
+// 2^62 under two, whose entries ask W <= 2^61), so the least key is the
 // rule's s* whether the window is empty or not, and the reduction's shape does
 // not matter.  The same pass carries the least and the greatest feasible s
 // (min / max, which commute): s_lo, s_hi, and feasible = there is one.
@@ -522,16 +526,18 @@ __device__ __forceinline__ void pick_block(Pick& a, u64 (*wk)[SL_THREADS / 64], 
 
 __global__ __launch_bounds__(SL_THREADS) void k_sweepw_select(const u64* __restrict__ profw,
                                                               const u64* __restrict__ prefix, unsigned n, u64 total,
-                                                              u64 max_part, u64* __restrict__ part) {
+                                                              u64 bound0, u64 bound1, u64* __restrict__ part) {
     __shared__ u64 wk[2][SL_THREADS / 64];
     __shared__ unsigned wu[3][SL_THREADS / 64];
     Pick a{0ull, 0ull, SL_NONE, SL_NONE, 0u};
     const u64 step = u64(gridDim.x) * SL_THREADS;
     for (u64 s = 1ull + u64(blockIdx.x) * SL_THREADS + threadIdx.x; s < u64(n); s += step) {
         const u64 p = prefix[s], c = profw[s];
-        const u64 twice = 2ull * p, d = twice >= total ? twice - total : total - twice;
-        // (p <= W for the prefix a scan left; a greater one would wrap to a side above L_max)
-        const bool feasible = p <= max_part && total - p <= max_part;
+        // the slack difference |(W - p - L0) - (p - L1)| (§16) as |(2 p + L0) - (W + L1)|: both terms stay below
+        // 2^64, and with L0 = L1 = L_max it is §13's |2 p - W|
+        const u64 x = 2ull * p + bound0, y = total + bound1, d = x >= y ? x - y : y - x;
+        // (p <= W for the prefix a scan left; a greater one would wrap to a side above its bound)
+        const bool feasible = p <= bound1 && total - p <= bound0;
         pick_merge(a, feasible ? c : (1ull << 63) | d, feasible ? d : c, unsigned(s), feasible ? unsigned(s) : SL_NONE,
                    feasible ? unsigned(s) : 0u);
     }
@@ -659,10 +665,10 @@ int sweepw_select_blocks(int n) {
 }
 
 void sweepw_select(hipStream_t s, const u64* profw, const u64* prefix, const unsigned* profile, int n, u64 total,
-                   u64 max_part, u64* part, const unsigned* span_part, int nspan, long long* rec) {
+                   u64 bound0, u64 bound1, u64* part, const unsigned* span_part, int nspan, long long* rec) {
     const int nb = sweepw_select_blocks(n);
-    hipLaunchKernelGGL(k_sweepw_select, dim3(nb), dim3(SL_THREADS), 0, s, profw, prefix, unsigned(n), total, max_part,
-                       part);
+    hipLaunchKernelGGL(k_sweepw_select, dim3(nb), dim3(SL_THREADS), 0, s, profw, prefix, unsigned(n), total, bound0,
+                       bound1, part);
     hipLaunchKernelGGL(k_sweepw_finish, dim3(1), dim3(SL_THREADS), 0, s, part, nb, profw, prefix, profile, unsigned(n),
                        span_part, nspan, rec);
 }

@@ -1,8 +1,10 @@
 // The multilevel bipartition (ek_multilevel_bipartition): host code over the
 // C-ABI, as kway.cpp is.  Coarsen by matching (ek_match) and contraction
 // (ek_hgr_contract) while a level still shrinks, split the coarsest level
-// spectrally under the node weights (ek_lanczos_fiedler, ek_sweep_cut_w), then
-// refine on the way back up (ek_fm_refine_w at every level).  No KL anywhere:
+// spectrally under the node weights (ek_lanczos_fiedler, ek_sweep_cut_wb), then
+// refine on the way back up (ek_fm_refine_wb at every level), both under the
+// sides' bounds: the symmetric L_max, where they are ek_sweep_cut_w and
+// ek_fm_refine_w, or the pair of ek_multilevel_bipartition_b.  No KL anywhere:
 // it swaps pairs and ignores weights.  Every step is an entry
 // point with a host checker of its own, so the driver is a composition and
 // nothing else: tests/test_gpu_multilevel.py composes the same V-cycle from the
@@ -27,9 +29,12 @@ void chk(int rc) {
 using Hgr = std::unique_ptr<ek_hgr, void (*)(ek_hgr*)>;
 
 // flags & EK_ML_WEIGHTED_LAPLACIAN: the coarsest level's Laplacian carries H_L's
-// net weights (ek_spmv_setup_pins_w); nothing else changes
-void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, int32_t flags, uint8_t* side_out,
-                 ek_ml_result* result) {
+// net weights (ek_spmv_setup_pins_w); nothing else changes.
+// bounds: the sides' bounds (L0, L1) of ek_multilevel_bipartition_b (DESIGN.md
+// §16); null: the symmetric bound L_max = floor((1 + imbalance) ceil(W / 2)) of
+// the other entries, under which the bounded sweep and FM are §13's and §12's.
+void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, int32_t flags, const int64_t* bounds,
+                 uint8_t* side_out, ek_ml_result* result) {
     const auto t0 = clk::now();
     if (flags & ~int32_t(EK_ML_WEIGHTED_LAPLACIAN))
         ek::fail(EK_EINVAL, "ek_multilevel_bipartition_ex: unknown flag bits 0x%x", unsigned(flags));
@@ -40,20 +45,29 @@ void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, int32_t f
     ek::ctx_ranks(ctx, &rank, &nranks);
     if (nranks > 1)
         ek::fail(EK_ESTATE, "ek_multilevel_bipartition: a multi-rank context (%d ranks); it runs on one", nranks);
-    if (!std::isfinite(o.imbalance) || o.imbalance < 0.0)
+    if (!bounds && (!std::isfinite(o.imbalance) || o.imbalance < 0.0))
         ek::fail(EK_EINVAL, "ek_multilevel_bipartition: imbalance %g (finite and >= 0)", o.imbalance);
     if (o.coarse_nodes < 8) o.coarse_nodes = 8;
     if (o.max_levels < 1 || o.max_levels > EK_ML_LEVELS) o.max_levels = EK_ML_LEVELS;
-    o.fm.imbalance = o.imbalance;
     ek_ml_result r{};
     for (int64_t v = 0; v < h.nodes; ++v) r.total_weight += h.node_w.empty() ? 1 : h.node_w[size_t(v)];
-    r.max_part = ek::refine_max_part(r.total_weight, 2, o.imbalance);
+    int64_t B[2];  // what the sweep and FM are given: within [0, W] (a bound above W holds nothing more)
+    if (bounds) {
+        ek::bounds_check("ek_multilevel_bipartition_b", r.total_weight, bounds);
+        B[0] = bounds[0];
+        B[1] = bounds[1];
+        r.max_part = std::max(B[0], B[1]);
+    } else {
+        r.max_part = ek::refine_max_part(r.total_weight, 2, o.imbalance);
+        B[0] = B[1] = std::min(r.max_part, r.total_weight);
+    }
     if (o.match.max_cluster <= 0) {
-        // a node no heavier than 2 L_max - W + 1 cannot make the weighted sweep
-        // jump over its window (§13); 4 W / coarse_nodes keeps the coarsest
-        // level's nodes comparable
+        // a node no heavier than L0 + L1 - W + 1 (2 L_max - W + 1) cannot make
+        // the weighted sweep jump over its window (§13, §16); 4 W / coarse_nodes
+        // keeps the coarsest level's nodes comparable
         const int64_t per = (4 * r.total_weight + o.coarse_nodes - 1) / o.coarse_nodes;
-        o.match.max_cluster = std::max<int64_t>(1, std::min(2 * r.max_part - r.total_weight + 1, per));
+        const int64_t room = bounds ? B[0] + B[1] - r.total_weight + 1 : 2 * r.max_part - r.total_weight + 1;
+        o.match.max_cluster = std::max<int64_t>(1, std::min(room, per));
     }
     r.max_cluster = o.match.max_cluster;
 
@@ -107,9 +121,8 @@ void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, int32_t f
     auto t = clk::now();
     ek_sweep_opts so;
     ek_sweep_default_opts(&so);
-    so.imbalance = o.imbalance;
-    ek_sweep_w_result sr{};
-    chk(ek_sweep_cut_w(ctx, cur, v.data(), &so, nullptr, nullptr, nullptr, &sr));
+    ek_sweep_wb_result sr{};
+    chk(ek_sweep_cut_wb(ctx, cur, v.data(), &so, B, nullptr, nullptr, nullptr, &sr));
     r.sweep_feasible = sr.feasible;
     std::vector<uint8_t> side(static_cast<size_t>(nc));
     chk(ek_rank_split(nc, v.data(), sr.n1, side.data()));
@@ -125,8 +138,8 @@ void bipartition(ek_ctx* ctx, const ek_hgr& h, const ek_ml_opts* opts, int32_t f
             side.swap(fine);
         }
         t = clk::now();
-        ek_fm_w_result fr{};
-        chk(ek_fm_refine_w(ctx, g, &o.fm, side.data(), nullptr, 0, nullptr, 0, &fr));
+        ek_fm_wb_result fr{};
+        chk(ek_fm_refine_wb(ctx, g, &o.fm, B, side.data(), nullptr, 0, nullptr, 0, &fr));
         r.t_fm += since(t);
         r.cut_before[l] = fr.cut_before;
         r.cut_after[l] = fr.cut;
@@ -187,7 +200,17 @@ int ek_multilevel_bipartition_ex(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts*
                                  ek_ml_result* result) {
     EK_TRY
     if (!ctx || !h || (h->nodes > 0 && !side_out)) ek::fail(EK_EINVAL, "ek_multilevel_bipartition: null argument");
-    bipartition(ctx, *h, opts, flags, side_out, result);
+    bipartition(ctx, *h, opts, flags, nullptr, side_out, result);
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_multilevel_bipartition_b(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* opts, int32_t flags,
+                                const int64_t bounds[2], uint8_t* side_out, ek_ml_result* result) {
+    EK_TRY
+    if (!ctx || !h || !bounds || (h->nodes > 0 && !side_out))
+        ek::fail(EK_EINVAL, "ek_multilevel_bipartition_b: null argument");
+    bipartition(ctx, *h, opts, flags, bounds, side_out, result);
     return EK_OK;
     EK_CATCH
 }
@@ -209,7 +232,7 @@ int ek_multilevel_bipartition_file_ex(ek_ctx* ctx, const char* path, const ek_ml
         own.resize(size_t(h->nodes));
         side_out = own.data();
     }
-    bipartition(ctx, *h, opts, flags, side_out, result);
+    bipartition(ctx, *h, opts, flags, nullptr, side_out, result);
     const std::vector<int32_t> part(side_out, side_out + h->nodes);
     ek::write_part_file(path, out_dir, 2, h->nodes, part.data());
     return EK_OK;

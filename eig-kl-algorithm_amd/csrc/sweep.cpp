@@ -58,6 +58,95 @@ bool net_span(const ek_hgr* h, int64_t e, const std::vector<int32_t>& pos, int32
     }
     return lo != hi;
 }
+// what the weighted sweep's steps leave, under either bound form
+struct SweepWCore {
+    int64_t n0 = 0, n1 = 0, s_lo = 0, s_hi = 0, feasible = 0, w0 = 0, w1 = 0, cut = 0, cut_nets = 0, cut_half = 0,
+            spanning_nets = 0;
+    double t_sort = 0.0, t_profile = 0.0, t_select = 0.0;
+    template <class R>
+    void store(R& r) const {
+        r.n0 = n0, r.n1 = n1, r.s_lo = s_lo, r.s_hi = s_hi, r.feasible = feasible, r.w0 = w0, r.w1 = w1, r.cut = cut;
+        r.cut_nets = cut_nets, r.cut_half = cut_half, r.spanning_nets = spanning_nets;
+        r.t_sort = t_sort, r.t_profile = t_profile, r.t_select = t_select;
+    }
+};
+
+// Steps 1-5 of the weighted rule (§13) under the per-side bounds of §16: side 1
+// of split s may weigh at most l1, side 0 at most l0, and the balance key is
+// the slack difference |(W - P - l0) - (P - l1)| = |2 P - W + (l0 - l1)|.  With
+// l0 = l1 = L_max this is §13 word for word.
+void sweepw_host_core(const ek_hgr* h, const double* v, int64_t W, int64_t l0, int64_t l1, int32_t* order_out,
+                      int64_t* profile_out, int64_t* prefix_out, SweepWCore& r) {
+    const int64_t n = h->nodes;
+
+    // 1. order
+    auto t = clk::now();
+    Keyed keyed;
+    std::vector<int32_t> pos;
+    order_by_key(v, n, keyed, pos);
+    r.t_sort = since(t);
+
+    // 2. the weighted and the count profile: +c / +1 at lo + 1, -c / -1 at hi + 1, inclusive prefix sums
+    // 3. P[s]: the running sum of w(order[r])
+    t = clk::now();
+    std::vector<int64_t> profw(static_cast<size_t>(n) + 1, 0), prof(static_cast<size_t>(n) + 1, 0),
+        prefix(static_cast<size_t>(n) + 1, 0);
+    for (int64_t e = 0; e < h->nets; ++e) {
+        int32_t lo = 0, hi = 0;
+        if (!net_span(h, e, pos, lo, hi)) continue;
+        const int64_t c = h->net_w.empty() ? 1 : h->net_w[size_t(e)];
+        ++r.spanning_nets;
+        profw[size_t(lo) + 1] += c;
+        profw[size_t(hi) + 1] -= c;
+        ++prof[size_t(lo) + 1];
+        --prof[size_t(hi) + 1];
+    }
+    for (int64_t s = 1; s <= n; ++s) {
+        profw[size_t(s)] += profw[size_t(s) - 1];
+        prof[size_t(s)] += prof[size_t(s) - 1];
+        const int32_t node = keyed[size_t(s) - 1].second;
+        prefix[size_t(s)] = prefix[size_t(s) - 1] + (h->node_w.empty() ? 1 : h->node_w[size_t(node)]);
+    }
+    r.t_profile = since(t);
+
+    // 4. the window; 5. the choice.  |2 P - W + (l0 - l1)| <= 2 W <= 2^63: 128 bits hold every step
+    t = clk::now();
+    auto dist = [&](int64_t s) {
+        const __int128 x = 2 * __int128(prefix[size_t(s)]) - W + (l0 - l1);
+        return uint64_t(x < 0 ? -x : x);
+    };
+    auto is_feasible = [&](int64_t s) { return prefix[size_t(s)] <= l1 && W - prefix[size_t(s)] <= l0; };
+    for (int64_t s = 1; s <= n - 1; ++s)
+        if (is_feasible(s)) {
+            if (!r.feasible) r.s_lo = s;
+            r.s_hi = s;
+            r.feasible = 1;
+        }
+    int64_t best = r.feasible ? r.s_lo : 1;
+    if (r.feasible) {
+        for (int64_t s = r.s_lo + 1; s <= r.s_hi; ++s) {  // least (profile_w, D, s): a later s only when strictly less
+            if (profw[size_t(s)] != profw[size_t(best)] ? profw[size_t(s)] < profw[size_t(best)] : dist(s) < dist(best))
+                best = s;
+        }
+    } else {
+        for (int64_t s = 2; s <= n - 1; ++s) {  // least (D, profile_w, s)
+            if (dist(s) != dist(best) ? dist(s) < dist(best) : profw[size_t(s)] < profw[size_t(best)]) best = s;
+        }
+    }
+    r.n1 = best;
+    r.n0 = n - best;
+    r.w1 = prefix[size_t(best)];
+    r.w0 = W - r.w1;
+    r.cut = profw[size_t(best)];
+    r.cut_nets = prof[size_t(best)];
+    r.cut_half = profw[size_t(n / 2)];
+    r.t_select = since(t);
+
+    if (order_out)
+        for (int64_t rnk = 0; rnk < n; ++rnk) order_out[rnk] = keyed[size_t(rnk)].second;
+    if (profile_out) std::copy(profw.begin(), profw.end(), profile_out);
+    if (prefix_out) std::copy(prefix.begin(), prefix.end(), prefix_out);
+}
 }  // namespace
 
 namespace ek {
@@ -109,6 +198,34 @@ ek_sweep_opts sweepw_check(const char* who, const ek_hgr* h, const double* v, co
     r.total_weight = total;
     r.max_part = refine_max_part(total, 2, o.imbalance);
     return o;
+}
+
+ek_sweep_opts sweepwb_check(const char* who, const ek_hgr* h, const double* v, const ek_sweep_opts* opts,
+                            const int64_t bounds[2], ek_sweep_wb_result& r) {
+    ek_sweep_opts o;
+    ek_sweep_default_opts(&o);
+    if (opts) o = *opts;
+    o.imbalance = 0.0;  // ignored: the bounds stand in its place
+    ek_sweep_w_result w{};
+    sweepw_check(who, h, v, &o, w);
+    if (!bounds) fail(EK_EINVAL, "%s: null bounds", who);
+    bounds_check(who, w.total_weight, bounds);
+    r = ek_sweep_wb_result{};
+    r.n = w.n;
+    r.total_weight = w.total_weight;
+    r.bound0 = bounds[0];
+    r.bound1 = bounds[1];
+    return o;
+}
+
+void bounds_check(const char* who, int64_t W, const int64_t bounds[2]) {
+    if (W > (int64_t(1) << 61)) fail(EK_EINVAL, "%s: total weight %lld above 2^61", who, (long long)W);
+    for (int s = 0; s < 2; ++s)
+        if (bounds[s] < 0 || bounds[s] > W)
+            fail(EK_EINVAL, "%s: bound %d = %lld outside [0, W = %lld]", who, s, (long long)bounds[s], (long long)W);
+    if (bounds[0] + bounds[1] < W)  // (both at most 2^61: the sum is exact)
+        fail(EK_EINVAL, "%s: bounds %lld + %lld below W = %lld", who, (long long)bounds[0], (long long)bounds[1],
+             (long long)W);
 }
 
 // `gKL2 <in> -EIG --sweep EPS [--sweep-ratio]` (cli.cpp refers to it weakly):
@@ -278,75 +395,22 @@ int ek_sweep_cut_w_host(const ek_hgr* h, const double* v, const ek_sweep_opts* o
     EK_TRY
     ek_sweep_w_result r{};
     ek::sweepw_check("ek_sweep_cut_w_host", h, v, opts, r);
-    const int64_t n = h->nodes, W = r.total_weight, lmax = r.max_part;
+    SweepWCore c;
+    sweepw_host_core(h, v, r.total_weight, r.max_part, r.max_part, order_out, profile_out, prefix_out, c);
+    c.store(r);
+    if (result) *result = r;
+    return EK_OK;
+    EK_CATCH
+}
 
-    // 1. order
-    auto t = clk::now();
-    Keyed keyed;
-    std::vector<int32_t> pos;
-    order_by_key(v, n, keyed, pos);
-    r.t_sort = since(t);
-
-    // 2. the weighted and the count profile: +c / +1 at lo + 1, -c / -1 at hi + 1, inclusive prefix sums
-    // 3. P[s]: the running sum of w(order[r])
-    t = clk::now();
-    std::vector<int64_t> profw(static_cast<size_t>(n) + 1, 0), prof(static_cast<size_t>(n) + 1, 0),
-        prefix(static_cast<size_t>(n) + 1, 0);
-    for (int64_t e = 0; e < h->nets; ++e) {
-        int32_t lo = 0, hi = 0;
-        if (!net_span(h, e, pos, lo, hi)) continue;
-        const int64_t c = h->net_w.empty() ? 1 : h->net_w[size_t(e)];
-        ++r.spanning_nets;
-        profw[size_t(lo) + 1] += c;
-        profw[size_t(hi) + 1] -= c;
-        ++prof[size_t(lo) + 1];
-        --prof[size_t(hi) + 1];
-    }
-    for (int64_t s = 1; s <= n; ++s) {
-        profw[size_t(s)] += profw[size_t(s) - 1];
-        prof[size_t(s)] += prof[size_t(s) - 1];
-        const int32_t node = keyed[size_t(s) - 1].second;
-        prefix[size_t(s)] = prefix[size_t(s) - 1] + (h->node_w.empty() ? 1 : h->node_w[size_t(node)]);
-    }
-    r.t_profile = since(t);
-
-    // 4. the window; 5. the choice.  |2 P - W| <= W <= 2^62 and 2 P <= 2^63: unsigned
-    t = clk::now();
-    auto dist = [&](int64_t s) {
-        const uint64_t twice = 2 * uint64_t(prefix[size_t(s)]), w = uint64_t(W);
-        return twice >= w ? twice - w : w - twice;
-    };
-    auto is_feasible = [&](int64_t s) { return prefix[size_t(s)] <= lmax && W - prefix[size_t(s)] <= lmax; };
-    for (int64_t s = 1; s <= n - 1; ++s)
-        if (is_feasible(s)) {
-            if (!r.feasible) r.s_lo = s;
-            r.s_hi = s;
-            r.feasible = 1;
-        }
-    int64_t best = r.feasible ? r.s_lo : 1;
-    if (r.feasible) {
-        for (int64_t s = r.s_lo + 1; s <= r.s_hi; ++s) {  // least (profile_w, |2P - W|, s): a later s only when strictly less
-            if (profw[size_t(s)] != profw[size_t(best)] ? profw[size_t(s)] < profw[size_t(best)] : dist(s) < dist(best))
-                best = s;
-        }
-    } else {
-        for (int64_t s = 2; s <= n - 1; ++s) {  // least (|2P - W|, profile_w, s)
-            if (dist(s) != dist(best) ? dist(s) < dist(best) : profw[size_t(s)] < profw[size_t(best)]) best = s;
-        }
-    }
-    r.n1 = best;
-    r.n0 = n - best;
-    r.w1 = prefix[size_t(best)];
-    r.w0 = W - r.w1;
-    r.cut = profw[size_t(best)];
-    r.cut_nets = prof[size_t(best)];
-    r.cut_half = profw[size_t(n / 2)];
-    r.t_select = since(t);
-
-    if (order_out)
-        for (int64_t rnk = 0; rnk < n; ++rnk) order_out[rnk] = keyed[size_t(rnk)].second;
-    if (profile_out) std::copy(profw.begin(), profw.end(), profile_out);
-    if (prefix_out) std::copy(prefix.begin(), prefix.end(), prefix_out);
+int ek_sweep_cut_wb_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opts, const int64_t bounds[2],
+                         int32_t* order_out, int64_t* profile_out, int64_t* prefix_out, ek_sweep_wb_result* result) {
+    EK_TRY
+    ek_sweep_wb_result r{};
+    ek::sweepwb_check("ek_sweep_cut_wb_host", h, v, opts, bounds, r);
+    SweepWCore c;
+    sweepw_host_core(h, v, r.total_weight, r.bound0, r.bound1, order_out, profile_out, prefix_out, c);
+    c.store(r);
     if (result) *result = r;
     return EK_OK;
     EK_CATCH

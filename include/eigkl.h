@@ -78,9 +78,11 @@ void ek_hgr_free(ek_hgr* h);
 /* Optional weights.  A hypergraph may carry a node weight w(v) >= 0 per node
  * and a net weight c(e) >= 1 per net (int32); an absent array stands for all
  * ones.  Only the weighted FM refinement, the weighted sweep cut
- * (ek_sweep_cut_w*) and ek_bipart_metrics_host read them: the Laplacian, the
- * KL graph, the Lanczos solve, the median, rank and count-sweep splits, KL, the
- * k-way paths and ek_fm_refine work on the structure alone.  ek_hgr_write writes a
+ * (ek_sweep_cut_w*), the matching, the multilevel paths over them
+ * (ek_multilevel_bipartition*, ek_partition_kway_ml) and the weighted metrics
+ * read them: the Laplacian, the KL graph, the Lanczos solve, the median, rank
+ * and count-sweep splits, KL, ek_partition_kway, ek_kway_refine and
+ * ek_fm_refine work on the structure alone.  ek_hgr_write writes a
  * weighted hypergraph in the hMETIS form below (fmt, the net weights, the node
  * weight lines) and an unweighted one as before; ek_hgr_induce and
  * ek_hgr_largest_component carry the kept nodes' and the surviving nets'
@@ -996,6 +998,142 @@ int ek_multilevel_bipartition_ex(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts*
                                  uint8_t* side_out /* nodes */, ek_ml_result* result);
 int ek_multilevel_bipartition_file_ex(ek_ctx* ctx, const char* path, const ek_ml_opts* opts, const char* out_dir,
                                       int32_t flags, uint8_t* side_out, ek_ml_result* result);
+
+/* ------------------------------------------------------------------ */
+/* Per-side weight bounds: the weighted sweep, the weighted FM and the   */
+/* V-cycle under B = (L0, L1), and the k-way partition by recursive       */
+/* multilevel bisection over them.  No reference          */
+/* counterpart.                                                           */
+/* ------------------------------------------------------------------ */
+/* bounds[s] = L_s is the greatest weight side s may hold.  0 <= L_s <= W, L0 +
+ * L1 >= W and W <= 2^61, each EK_EINVAL otherwise (a caller clamps a looser
+ * bound to W).  The slack difference of side weights (S0, S1) is D(S0, S1) =
+ * |(S0 - L0) - (S1 - L1)|; with L0 = L1 it is |S0 - S1|.
+ *
+ * The bounded sweep is the rule of ek_sweep_cut_w with three replacements.
+ * Split s is feasible iff P[s] <= L1 and W - P[s] <= L0 (side 1 of split s
+ * weighs P[s]).  Wherever that rule compares |2 P[s] - W| it compares D(W -
+ * P[s], P[s]) = |2 P[s] - W + (L0 - L1)|, in the feasible choice and in the
+ * fallback alike.  The feasible splits are one contiguous range, certainly not
+ * empty when max w(v) <= L0 + L1 - W + 1.  opts->imbalance is ignored and
+ * objective must be 0.  With L0 = L1 = floor((1 + eps) ceil(W / 2)) the
+ * entries reproduce ek_sweep_cut_w* at imbalance eps exactly. */
+typedef struct {
+    int64_t n, n0, n1;        /* nodes; side 0 and side 1 of the chosen split (n1 = s*) */
+    int64_t s_lo, s_hi;       /* the feasible splits (0, 0 when there is none) */
+    int64_t feasible;         /* 1: the window is not empty */
+    int64_t total_weight;     /* W */
+    int64_t bound0, bound1;   /* L0, L1 */
+    int64_t w0, w1;           /* the sides' weights at s*: W - P[s*], P[s*] */
+    int64_t cut;              /* profile_w[s*] */
+    int64_t cut_nets;         /* the count profile at s* */
+    int64_t cut_half;         /* profile_w[floor(n / 2)] */
+    int64_t spanning_nets;    /* nets with lo < hi */
+    double t_sort, t_profile, t_select; /* wall seconds (host clock) */
+} ek_sweep_wb_result;
+/* The checker: single threaded, written from the rule.  Arguments as
+ * ek_sweep_cut_w_host plus the bounds. */
+int ek_sweep_cut_wb_host(const ek_hgr* h, const double* v, const ek_sweep_opts* opts, const int64_t bounds[2],
+                         int32_t* order_out, int64_t* profile_out /* n + 1 */, int64_t* prefix_out /* n + 1 */,
+                         ek_sweep_wb_result* result);
+/* The same on the GPU: the same order, profile_w, P and result integers. */
+int ek_sweep_cut_wb(ek_ctx* ctx, const ek_hgr* h, const double* v_host, const ek_sweep_opts* opts,
+                    const int64_t bounds[2], int32_t* order_out, int64_t* profile_out /* n + 1 */,
+                    int64_t* prefix_out /* n + 1 */, ek_sweep_wb_result* result);
+
+/* The bounded FM is the rule of ek_fm_refine_w with these replacements.
+ * (c) side a's top node is a candidate iff S[1 - a] + w(top) <= L_(1-a).
+ * d_t = D(S_0, S_1).  (d) on equal g the candidate whose side has less slack
+ * (greater S_a - L_a) moves, then the smaller id.  A side already above its
+ * bound never receives.  opts->imbalance is ignored.  A pass_log row ends with
+ * D after the rollback.  With L0 = L1 = floor((1 + eps) ceil(W / 2)) the
+ * entries reproduce ek_fm_refine_w* at imbalance eps exactly. */
+typedef struct {
+    int64_t n, total_weight, bound0, bound1; /* nodes; W; L0, L1 */
+    int32_t passes, passes_run;        /* counted passes (t* > 0); passes run (at most one more) */
+    int64_t moves_tried, moves_kept;   /* sum of t and of t* over the passes run */
+    int64_t cut_before, cut;           /* the weighted cut of the sides given and of the sides returned */
+    int64_t cut_nets_before, cut_nets; /* the cut nets of the same */
+    int64_t w0, w1, n0, n1;            /* the sides' weights and node counts after the run */
+    double t_setup, t_passes, t_metrics; /* wall seconds (host clock) */
+} ek_fm_wb_result;
+int ek_fm_refine_wb_host(const ek_hgr* h, const ek_fm_opts* opts, const int64_t bounds[2], uint8_t* side_inout /* nodes */,
+                         int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log, int64_t move_cap,
+                         ek_fm_wb_result* result);
+int ek_fm_refine_wb(ek_ctx* ctx, const ek_hgr* h, const ek_fm_opts* opts, const int64_t bounds[2],
+                    uint8_t* side_inout /* nodes */, int64_t* pass_log, int64_t log_passes, ek_fm_move* move_log,
+                    int64_t move_cap, ek_fm_wb_result* result);
+
+/* ek_multilevel_bipartition_ex with ek_sweep_cut_wb and ek_fm_refine_wb in
+ * place of ek_sweep_cut_w and ek_fm_refine_w.  opts->imbalance is ignored.
+ * The default max_cluster is max(1, min(L0 + L1 - W + 1, ceil(4 W /
+ * coarse_nodes))).  result->max_part reports max(L0, L1). */
+int ek_multilevel_bipartition_b(ek_ctx* ctx, const ek_hgr* h, const ek_ml_opts* opts, int32_t flags,
+                                const int64_t bounds[2], uint8_t* side_out /* nodes */, ek_ml_result* result);
+
+/* The bounds of one bisection of the k-way recursion (host).  A block of
+ * weight Wb destined for kb >= 2 parts splits as ek_kway_plan does: side 0
+ * gets k_0 = ceil(kb / 2) parts, side 1 k_1 = floor(kb / 2).  out[s] = min(k_s
+ * part_bound, floor(mult ceil(Wb k_s / kb))), then clamped to Wb.  If Wb <= kb
+ * part_bound then out[0] + out[1] >= Wb, and a side within out[s] satisfies
+ * that premise for its own bisections.  EK_EINVAL for Wb < 0,
+ * kb outside 2..256, part_bound < 0, mult not finite or < 1, a null out. */
+int ek_kway_bisect_bounds(int64_t Wb, int32_t kb, int64_t part_bound, double mult, int64_t out[2]);
+
+/* out[0] = cut nets (lambda_e >= 2), out[1] = the connectivity sum(lambda_e -
+ * 1), out[2] = the weighted connectivity sum c(e)(lambda_e - 1), out[3] = SOED,
+ * out[4 + p] = the node weight of part p, p < k.  lambda_e and the nets that
+ * count: the conventions of ek_kway_metrics_host.  Weights: h's, 1 where it
+ * carries none.  EK_EINVAL for k outside 1..256 or a part id outside [0, k). */
+int ek_kway_metrics_w_host(const ek_hgr* h, const int32_t* part /* nodes */, int32_t k, int64_t* out /* 4 + k */);
+/* The same on the GPU (int64 sums by integer atomics). */
+int ek_kway_metrics_w(ek_ctx* ctx, const ek_hgr* h, const int32_t* part /* nodes */, int32_t k,
+                      int64_t* out /* 4 + k */);
+
+typedef struct {
+    int32_t k;             /* number of parts, 2..256 */
+    int32_t flags;         /* ek_multilevel_bipartition_ex's */
+    double imbalance;      /* epsilon >= 0; default 0.03: part_bound = floor((1 + eps) ceil(W / k)) */
+    int32_t write_results; /* ek_partition_kway_ml_file: 1 writes results/<base>.part.<k> under out_dir */
+    int32_t pad;
+    const char* out_dir;   /* NULL: the CWD */
+    ek_ml_opts ml;         /* coarse_nodes, max_levels, match, fm, lanczos of every bisection; ml.imbalance is ignored */
+} ek_kway_ml_opts;
+
+typedef struct {
+    int32_t k;
+    int32_t bisections;         /* bisections run (blocks of >= 2 nodes destined for >= 2 parts) */
+    int32_t coarsest_fallbacks; /* of which split their coarsest level by node index */
+    int32_t infeasible_sweeps;  /* of which had no feasible sweep split */
+    int64_t total_weight, part_bound; /* W; Lk = floor((1 + imbalance) ceil(W / k)) */
+    int64_t part_w_min, part_w_max;   /* lightest / heaviest part */
+    int64_t parts_over_bound, empty_parts; /* parts above Lk; parts of no node */
+    int64_t cut_nets, connectivity, connectivity_w, soed; /* ek_kway_metrics_w of part_out */
+    int64_t levels_total, fm_moves;   /* coarse levels and kept FM moves, summed over the bisections */
+    /* wall seconds (host clock): the sub-hypergraphs, the bisections, the metrics, all; the bisections' phases */
+    double t_induce, t_ml, t_metrics, t_total;
+    double t_match, t_contract, t_lanczos, t_sweep, t_fm;
+    double t_level[EK_KWAY_LEVELS]; /* per recursion level (root = 0), its blocks' induce + bisections */
+} ek_kway_ml_result;
+
+void ek_kway_ml_default_opts(ek_kway_ml_opts* o);
+/* k-way partition of h by recursive multilevel bisection, depth first, side 0
+ * before side 1, as ek_partition_kway recurses: a block is ek_hgr_induce'd
+ * (weights carried), its bounds come from ek_kway_bisect_bounds with
+ * part_bound = Lk and mult = (1 + imbalance)^(1 / ceil(log2 k)) (1 + imbalance
+ * itself when ceil(log2 k) = 1), and it is bisected by
+ * ek_multilevel_bipartition_b.  A block of fewer than 2 nodes gives all its
+ * nodes the id `base` with no bisection.  Empty parts are allowed and counted.
+ * With unit node weights every part weighs at most Lk; with arbitrary weights a
+ * part may end above it (parts_over_bound), which is reported, not an error.
+ * EK_ESTATE on a multi-rank context; EK_EINVAL unless 2 <= k <= 256.  result
+ * may be NULL.  Keeps nothing on the context beyond what its pieces do. */
+int ek_partition_kway_ml(ek_ctx* ctx, const ek_hgr* h, const ek_kway_ml_opts* opts, int32_t* part_out /* nodes */,
+                         ek_kway_ml_result* result);
+/* The same on the hMETIS reading of a file (ek_hgr_read_weighted); part_out
+ * may be NULL.  With write_results: results/<base>.part.<k> under out_dir. */
+int ek_partition_kway_ml_file(ek_ctx* ctx, const char* path, const ek_kway_ml_opts* opts, int32_t* part_out,
+                              ek_kway_ml_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
