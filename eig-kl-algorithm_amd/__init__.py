@@ -118,6 +118,14 @@ class KwayRefineResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _REFINE_TIMES])
 
 
+class KwayRefineWResult(_AbiStruct):
+    _fields_ = ([("k", _I32), ("rounds", _I32)]
+                + [(k, _I64) for k in ("moves", "gain_total", "total_weight", "bound_min", "bound_max", "part_w_min",
+                                       "part_w_max", "parts_over_bound", "connectivity_w_before", "cut_nets",
+                                       "connectivity", "connectivity_w", "soed")]
+                + [(k, ctypes.c_double) for k in _REFINE_TIMES])
+
+
 class SweepOpts(_AbiStruct):
     _fields_ = [("objective", _I32), ("pad", _I32), ("imbalance", ctypes.c_double)]
 
@@ -338,6 +346,10 @@ _sig("ek_kway_refine_host", ctypes.c_int, _P, ctypes.POINTER(KwayRefineOpts), _P
      ctypes.POINTER(KwayRefineResult))
 _sig("ek_kway_refine", ctypes.c_int, _P, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _I64,
      ctypes.POINTER(KwayRefineResult))
+_sig("ek_kway_refine_w_host", ctypes.c_int, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _P, _I64,
+     ctypes.POINTER(KwayRefineWResult))
+_sig("ek_kway_refine_w", ctypes.c_int, _P, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _P, _I64,
+     ctypes.POINTER(KwayRefineWResult))
 _sig("ek_sweep_default_opts", None, ctypes.POINTER(SweepOpts))
 _sig("ek_sweep_cut_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
 _sig("ek_sweep_cut", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
@@ -674,6 +686,38 @@ def kway_refine_host(hgr, part, k, imbalance=0.03, max_rounds=0):
     (ek_kway_refine_host, the device path's checker).  Returns (part, result dict, round log)."""
     return _kway_refine(lambda *a: _lib.ek_kway_refine_host(hgr._h, *a), "kway_refine_host", hgr, part, k,
                         imbalance, max_rounds)
+
+
+def _kway_refine_w(call, what, hgr, part, k, imbalance, max_rounds, bounds):
+    """_kway_refine for the weighted entries: bounds is None (the uniform bound at `imbalance`) or k int64 values."""
+    start = np.ascontiguousarray(part, np.int32)
+    if len(start) != hgr.nodes:
+        raise ValueError(f"part has {len(start)} entries for {hgr.nodes} nodes")
+    if bounds is not None:
+        bounds = np.ascontiguousarray(bounds, np.int64)
+        if len(bounds) != int(k):
+            raise ValueError(f"{len(bounds)} bounds for {k} parts")
+    o = KwayRefineOpts()
+    _lib.ek_kway_refine_default_opts(ctypes.byref(o))
+    o.k, o.max_rounds, o.imbalance = int(k), int(max_rounds), float(imbalance)
+    cap = int(max_rounds) if max_rounds > 0 else 1024
+    while True:
+        out = start.copy()
+        log = np.zeros((cap, 4), np.int64)
+        r = KwayRefineWResult()
+        _chk(call(ctypes.byref(o), _p(bounds), _p(out), _p(log), cap, ctypes.byref(r)), what)
+        if r.rounds <= cap:  # (else: deterministic, so the same run again with room for its log)
+            break
+        cap = r.rounds
+    return out, {name: getattr(r, name) for name, _ in KwayRefineWResult._fields_}, log[:r.rounds].copy()
+
+
+def kway_refine_w_host(hgr, part, k, imbalance=0.03, max_rounds=0, bounds=None):
+    """Weighted k-way connectivity refinement under per-part weight bounds, on the host (ek_kway_refine_w_host, the
+    device path's checker): hgr's node weights under bounds[p], or under floor((1 + imbalance) ceil(W / k)) when
+    bounds is None, its net weights in the connectivity.  Returns (part, result dict, round log)."""
+    return _kway_refine_w(lambda *a: _lib.ek_kway_refine_w_host(hgr._h, *a), "kway_refine_w_host", hgr, part, k,
+                          imbalance, max_rounds, bounds)
 
 
 def _sweep_opts(imbalance, ratio):
@@ -1290,6 +1334,12 @@ class Context:
         round log.  Returns (part, result dict, round log)."""
         return _kway_refine(lambda *a: _lib.ek_kway_refine(self._c, hgr._h, *a), "kway_refine", hgr, part, k,
                             imbalance, max_rounds)
+
+    def kway_refine_w(self, hgr, part, k, imbalance=0.03, max_rounds=0, bounds=None):
+        """kway_refine_w_host on the GPU (ek_kway_refine_w): the same part vector, result integers and
+        round log.  Returns (part, result dict, round log)."""
+        return _kway_refine_w(lambda *a: _lib.ek_kway_refine_w(self._c, hgr._h, *a), "kway_refine_w", hgr, part, k,
+                              imbalance, max_rounds, bounds)
 
     def match(self, hgr, max_cluster=2, max_net=64, max_rounds=8):
         """match_host on the GPU (ek_match): the same mate, cluster, round log and result integers."""

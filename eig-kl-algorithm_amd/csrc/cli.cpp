@@ -79,6 +79,13 @@
 //                        --ml-coarse, --ml-weighted-laplacian, --fm-passes and
 //                        --fm-stall apply -> results/<base>.part.<N>; one line
 //                        beginning "k-way-ml:"
+//   --refine-weighted EPS2  with --kway-multilevel: then the weighted k-way
+//                        refinement on the device (ek_kway_refine_w) on the same
+//                        reading of the file, under the uniform bound
+//                        floor((1 + EPS2) ceil(W / N)); --refine-rounds applies;
+//                        the refined vector is what results/<base>.part.<N>
+//                        holds, and one more line beginning "refine-w:" is
+//                        printed
 //   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
 //                        carries its net weights (EK_ML_WEIGHTED_LAPLACIAN,
 //                        -(2 c(e) / |e|) per pin pair); the "ml:" line ends
@@ -137,6 +144,12 @@ int ml_file_for_cli(ek_ctx* ctx, const char* path, const ek_lanczos_opts* lanczo
 int kway_ml_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
                          int coarse_nodes, int max_passes, int stall, int32_t flags, ek_kway_ml_result* r)
     __attribute__((weak));
+// kway_refine_w.cpp: ek_partition_kway_ml on the hMETIS reading of the file, then ek_kway_refine_w, then the
+// results file, for `--k N --kway-multilevel EPS --refine-weighted EPS2`
+int kway_ml_refine_w_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                                  int coarse_nodes, int max_passes, int stall, int32_t flags, double refine_imbalance,
+                                  int max_rounds, ek_kway_ml_result* mr, ek_kway_refine_w_result* rr)
+    __attribute__((weak));
 }
 
 namespace {
@@ -159,6 +172,8 @@ struct Opts {
     bool ml = false, ml_sub = false;  // --multilevel EPS; --ml-coarse or --ml-weighted-laplacian seen
     bool ml_wlap = false;             // --ml-weighted-laplacian
     bool kml = false;                 // --kway-multilevel EPS (sets ml and ml_eps too): with --k, the k-way driver
+    bool refine_w = false;            // --refine-weighted EPS2 (with --kway-multilevel)
+    double refine_w_eps = 0.0;
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -469,6 +484,9 @@ constexpr const char* ML_USAGE =
     "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> [--ml-coarse <N>] "
     "[--ml-weighted-laplacian]  (the k-way partition by recursive multilevel bisection; needs --k with 2 <= parts <= "
     "256, excludes --multilevel and --refine)\n"
+    "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> --refine-weighted <imbalance> "
+    "[--refine-rounds <R>]  (then the weighted k-way refinement under floor((1 + imbalance) ceil(W / parts)); needs "
+    "--kway-multilevel; the refine-w: line follows)\n"
     "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> --ml-weighted-laplacian  (the coarsest level's Laplacian "
     "carries its net weights, -(2 c(e) / |e|) per pin pair; needs --multilevel; the ml: line ends with wlap=1)\n";
 
@@ -500,9 +518,18 @@ int run_kway_ml(const Opts& o) {
     const ek_solve_opts so = solve_opts(o);
     if (!ek::kway_ml_file_for_cli) throw Fail{"this build carries no multilevel k-way path"};
     ek_kway_ml_result r{};
-    check(ek::kway_ml_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse, o.fm_passes,
-                                   o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0, &r),
-          "multilevel k-way partition");
+    ek_kway_refine_w_result rr{};
+    if (o.refine_w) {
+        if (!ek::kway_ml_refine_w_file_for_cli) throw Fail{"this build carries no weighted k-way refinement"};
+        check(ek::kway_ml_refine_w_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse,
+                                                o.fm_passes, o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0,
+                                                o.refine_w_eps, o.refine_rounds, &r, &rr),
+              "multilevel k-way partition and weighted refinement");
+    } else {
+        check(ek::kway_ml_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse,
+                                       o.fm_passes, o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0, &r),
+              "multilevel k-way partition");
+    }
     std::printf("k-way-ml: k %d, imbalance %g, bisections %d, fallbacks %d, infeasible %d, total_weight %lld, part_bound "
                 "%lld, part weights %lld..%lld, over_bound %lld, empty %lld, cut nets %lld, connectivity %lld, "
                 "connectivity_w %lld, SOED %lld, levels %lld, fm_moves %lld, %.3f s (induce %.3f, match %.3f, contract "
@@ -513,6 +540,12 @@ int run_kway_ml(const Opts& o) {
                 (long long)r.levels_total, (long long)r.fm_moves, r.t_total, r.t_induce, r.t_match, r.t_contract,
                 r.t_lanczos, r.t_sweep, r.t_fm, r.t_metrics, secs(t0), base_name(o.input).c_str(), r.k,
                 o.ml_wlap ? ", wlap=1" : "");
+    if (o.refine_w)
+        std::printf("refine-w: imbalance %g (bound %lld), %d rounds, %lld moves, connectivity_w %lld -> %lld, cut nets "
+                    "%lld, part weights %lld..%lld, over_bound %lld, %.3f s\n", o.refine_w_eps, (long long)rr.bound_max,
+                    rr.rounds, (long long)rr.moves, (long long)rr.connectivity_w_before, (long long)rr.connectivity_w,
+                    (long long)rr.cut_nets, (long long)rr.part_w_min, (long long)rr.part_w_max,
+                    (long long)rr.parts_over_bound, rr.t_setup + rr.t_rounds + rr.t_metrics);
     return 0;
 }
 
@@ -553,6 +586,12 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.refine = true;
                 if (!std::isfinite(o.refine_eps) || o.refine_eps < 0) throw Fail{"--refine takes an imbalance >= 0"};
             } else if (a == "--refine-rounds") o.refine_rounds = std::stoi(need("--refine-rounds"));
+            else if (a == "--refine-weighted") {
+                o.refine_w = true;  // (before the value: a missing or bad one ends in the usage text below)
+                o.refine_w_eps = std::stod(need("--refine-weighted"));
+                if (!std::isfinite(o.refine_w_eps) || o.refine_w_eps < 0)
+                    throw Fail{"--refine-weighted takes an imbalance >= 0"};
+            }
             else if (a == "--sweep") {
                 o.sweep_eps = std::stod(need("--sweep"));
                 o.sweep = true;
@@ -599,16 +638,20 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         } catch (const Fail& e) {
             std::fprintf(stderr, "Error: %s\n", e.msg.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
-            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel") std::printf("%s", ML_USAGE);
+            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted") std::printf("%s", ML_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
-            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel") std::printf("%s", ML_USAGE);
+            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted") std::printf("%s", ML_USAGE);
             return 1;
         }
     }
     try {
+        if (o.refine_w && !o.kml) {  // --refine-weighted follows --kway-multilevel only
+            std::printf("%s", ML_USAGE);
+            return 1;
+        }
         if (o.ml || o.ml_sub) {
             if (!o.ml || (o.kml ? o.kway < 2 || o.kway > 256 : o.kway != 0) || o.refine || o.sweep || o.sweep_ratio || o.fm || o.weighted || o.sweep_weighted ||
                 o.no_kl || o.tool != "gKL2" || !(pos.size() == 2 && pos[1] == "-EIG")) {

@@ -245,6 +245,18 @@ void fmwb_prepare(const char* who, const ek_hgr* h, const ek_fm_opts* opts, cons
 // cw, w and the range rules; returns W
 int64_t weights_prepare(const char* who, const ek_hgr* h, WeightedInput& out);
 
+// kway_refine_w.cpp — what the host and the device weighted k-way refinement
+// (§17) share: the input.  refine_check (the imbalance ignored when bounds are
+// given), weights_prepare, W, and L_p of every part: bounds[p] (each >= 0,
+// EK_EINVAL otherwise) or refine_max_part(W, k, imbalance) for all
+struct RefineWInput : WeightedInput {
+    int64_t total = 0;
+    std::vector<int64_t> bound;  // k
+    ek_kway_refine_opts opts;
+};
+void refine_w_prepare(const char* who, const ek_hgr* h, const ek_kway_refine_opts* opts, const int64_t* bounds,
+                      const int32_t* part, RefineWInput& out);
+
 // match.cpp — what the host and the device matching share: the argument checks
 // (EK_EINVAL as eigkl.h lists it; the opts with the defaults filled in) and the
 // input, weights_prepare's
@@ -805,6 +817,34 @@ struct RefineDev {
 // slot (device, zero before the round): the round's candidates, independent
 // candidates, accepted moves and gain.  nets > 0.
 void refine_round(hipStream_t s, const RefineDev& d, unsigned long long* slot);
+// the three launches of a round that read no weights, each by itself, for the
+// weighted round (kernels_refine_w.hip): k_refine_masks, k_refine_winner and
+// k_refine_indep (slot[1]: the list's length)
+void refine_masks(hipStream_t s, int nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* part,
+                  unsigned long long* masks);
+void refine_winner(hipStream_t s, int nets, const int64_t* net_ptr, const int32_t* pins, const unsigned long long* key,
+                   unsigned long long* win);
+void refine_indep(hipStream_t s, int n, const int64_t* inc_ptr, const int32_t* inc, const unsigned long long* key,
+                  const unsigned long long* win, unsigned long long* list, unsigned long long* slot);
+// the node kernels' grid (k_refine_gain, k_refine_indep): one wave a 64 nodes, capped
+unsigned refine_node_blocks(int n);
+
+// kernels_refine_w.hip — one round of the weighted k-way refinement
+// (ek_kway_refine_w, §17): RefineDev's arrays with 64-bit part weights and
+// per-part bounds in place of sizes and lmax
+struct RefineWDev {
+    int n, nets, k;
+    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
+    const int32_t *pins, *inc, *cw, *w;  // c(e) per participating net, w(v) per node
+    uint8_t* part;                       // n
+    long long* S;                        // 256: the parts' weights
+    const long long* L;                  // 256: their bounds
+    unsigned long long* masks;           // 8 a net: Lambda(e), U(e)
+    unsigned long long *key, *win, *list, *thr;  // n, nets, n, 256
+    uint8_t* tgt;                        // n
+};
+// slot as refine_round's.  nets > 0.
+void refine_w_round(hipStream_t s, const RefineWDev& d, unsigned long long* slot);
 
 // kernels_sweep.hip — the sweep cuts (ek_sweep_cut, ek_sweep_cut_w): sort,
 // scans, the count and the weighted profile, prefix weights, the two choices

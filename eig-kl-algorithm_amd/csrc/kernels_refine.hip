@@ -361,5 +361,29 @@ void refine_round(hipStream_t s, const RefineDev& d, u64* slot) {
     hipLaunchKernelGGL(k_refine_apply, dim3(256), dim3(RF_THREADS), 0, s, d.list, d.tgt, d.thr, d.part, d.sizes, slot);
 }
 
+// The launches that read no weights, one by one, with refine_round's grids:
+// the weighted round (kernels_refine_w.hip) puts its own gain, select and
+// apply kernels between them.
+unsigned refine_node_blocks(int n) {
+    const long long node_waves = (n + 63ll) / 64;
+    return unsigned(std::max<long long>(std::min<long long>((node_waves + RF_WAVES - 1) / RF_WAVES, RF_MAX_BLOCKS), 1));
+}
+
+void refine_masks(hipStream_t s, int nets, const int64_t* net_ptr, const int32_t* pins, const uint8_t* part, u64* masks) {
+    hipLaunchKernelGGL(k_refine_masks, dim3(unsigned((nets + RF_THREADS - 1) / RF_THREADS)), dim3(RF_THREADS), 0, s, nets,
+                       net_ptr, pins, part, masks);
+}
+
+void refine_winner(hipStream_t s, int nets, const int64_t* net_ptr, const int32_t* pins, const u64* key, u64* win) {
+    hipLaunchKernelGGL(k_refine_winner, dim3(unsigned((nets + RF_THREADS - 1) / RF_THREADS)), dim3(RF_THREADS), 0, s, nets,
+                       net_ptr, pins, key, win);
+}
+
+void refine_indep(hipStream_t s, int n, const int64_t* inc_ptr, const int32_t* inc, const u64* key, const u64* win,
+                  u64* list, u64* slot) {
+    hipLaunchKernelGGL(k_refine_indep, dim3(refine_node_blocks(n)), dim3(RF_THREADS), 0, s, n, inc_ptr, inc, key, win,
+                       list, slot);
+}
+
 }  // namespace dev
 }  // namespace ek

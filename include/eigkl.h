@@ -79,8 +79,8 @@ void ek_hgr_free(ek_hgr* h);
  * and a net weight c(e) >= 1 per net (int32); an absent array stands for all
  * ones.  Only the weighted FM refinement, the weighted sweep cut
  * (ek_sweep_cut_w*), the matching, the multilevel paths over them
- * (ek_multilevel_bipartition*, ek_partition_kway_ml) and the weighted metrics
- * read them: the Laplacian, the KL graph, the Lanczos solve, the median, rank
+ * (ek_multilevel_bipartition*, ek_partition_kway_ml), the weighted k-way
+ * refinement (ek_kway_refine_w*) and the weighted metrics read them: the Laplacian, the KL graph, the Lanczos solve, the median, rank
  * and count-sweep splits, KL, ek_partition_kway, ek_kway_refine and
  * ek_fm_refine work on the structure alone.  ek_hgr_write writes a
  * weighted hypergraph in the hMETIS form below (fmt, the net weights, the node
@@ -1134,6 +1134,65 @@ int ek_partition_kway_ml(ek_ctx* ctx, const ek_hgr* h, const ek_kway_ml_opts* op
  * may be NULL.  With write_results: results/<base>.part.<k> under out_dir. */
 int ek_partition_kway_ml_file(ek_ctx* ctx, const char* path, const ek_kway_ml_opts* opts, int32_t* part_out,
                               ek_kway_ml_result* result);
+
+/* ------------------------------------------------------------------ */
+/* Weighted k-way connectivity refinement under per-part weight bounds. */
+/* No reference counterpart.                                             */
+/* ------------------------------------------------------------------ */
+/* The rule of ek_kway_refine on the weighted connectivity sum c(e)(lambda_e -
+ * 1) of a part vector, with node weights under the bounds.
+ * Input as ek_fm_refine_w: the nets with at least 2 distinct pins, each pin
+ * once; w(v) >= 0 and c(e) >= 1, 1 where h carries no such array; W = sum w(v);
+ * D(v) = the sum of c(e) over v's nets, at most 2^31 - 1; W and the sum of all
+ * c(e) at most 2^62.  S(p) is the weight of part p.  L_p, the bound of part p,
+ * is bounds[p] when bounds is given (k values, each >= 0; opts->imbalance is
+ * then ignored), otherwise floor((1 + imbalance) ceil(W / k)) for every part,
+ * ek_partition_kway_ml's part_bound.  One round, all of it read from the state
+ * at the round's start, with these replacements in ek_kway_refine's:
+ *  (a) r(v) = the sum of c(e) over v's nets in which v is its part's only pin,
+ *      c(v,b) the same over its nets with a pin in b, g(v,b) = (r(v) - D(v)) +
+ *      c(v,b), in that order inside int32: what moving v alone to b takes off
+ *      the weighted connectivity;
+ *  (b) part b (not v's own) is open for v iff S(b) + w(v) <= L_b; the target is
+ *      the open part of greatest g, ties to the smaller b, and v is a candidate
+ *      iff that g > 0;
+ *  (c) winners and independence as there; per part b the independent candidates
+ *      with target b in (g descending, id ascending) order, and the accepted set
+ *      is the LONGEST PREFIX of that order whose summed w(v) is at most L_b -
+ *      S(b): a node that does not fit ends the part's intake for the round, even
+ *      when a lighter, later one would fit; nodes of weight 0 directly after the
+ *      last fitting node are accepted, those after the first rejected are not;
+ *  (d) accepted nodes move; rounds repeat until one accepts nothing (not
+ *      counted, not logged) or max_rounds rounds have moved.
+ * Accepted nodes share no net, so the weighted connectivity falls by exactly the
+ * round's gain.  No part ends above max(L_p, its initial S(p)); a part already
+ * above its bound never receives, not even a node of weight 0; there is no
+ * lower bound on a part's weight.  With every weight 1 and no bounds the rule is
+ * ek_kway_refine's word for word. */
+typedef struct {
+    int32_t k, rounds;                     /* rounds that moved at least one node */
+    int64_t moves, gain_total;             /* accepted moves; connectivity_w_before - connectivity_w */
+    int64_t total_weight;                  /* W */
+    int64_t bound_min, bound_max;          /* least / greatest L_p as used */
+    int64_t part_w_min, part_w_max;        /* after the run */
+    int64_t parts_over_bound;              /* parts with S(p) > L_p after the run */
+    int64_t connectivity_w_before;
+    int64_t cut_nets, connectivity, connectivity_w, soed; /* ek_kway_metrics_w of the result */
+    double t_setup, t_rounds, t_metrics;   /* wall seconds (host clock) */
+} ek_kway_refine_w_result;
+
+/* The refinement on the host (no GPU): the checker of ek_kway_refine_w, single
+ * threaded and written from the rule.  Arguments as ek_kway_refine_host
+ * (ek_kway_refine_opts is reused), plus bounds (k values, or NULL).  EK_EINVAL
+ * as there, plus a bound < 0 and the weight ranges above. */
+int ek_kway_refine_w_host(const ek_hgr* h, const ek_kway_refine_opts* opts, const int64_t* bounds /* k, or NULL */,
+                          int32_t* part_inout, int64_t* round_log, int64_t log_rounds, ek_kway_refine_w_result* result);
+/* The same on the GPU: the same part vector, round log and result integers.
+ * Six launches a round; the host reads one 8-byte counter per round.  EK_ESTATE
+ * on a multi-rank context.  Keeps nothing on the context: every buffer is local
+ * to the call. */
+int ek_kway_refine_w(ek_ctx* ctx, const ek_hgr* h, const ek_kway_refine_opts* opts, const int64_t* bounds,
+                     int32_t* part_inout, int64_t* round_log, int64_t log_rounds, ek_kway_refine_w_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
