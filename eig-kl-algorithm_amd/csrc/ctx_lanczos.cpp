@@ -987,6 +987,28 @@ struct Solve {
         std::atomic_thread_fence(std::memory_order_acquire);
     }
 
+    double t_row(int i) const { return std::fabs(d[size_t(i)]) + (i > 0 ? std::fabs(e[size_t(i - 1)]) : 0.0); }
+
+    // The first step i in [max(from, 1), last] whose ||f_i|| (fn2v[i], squared)
+    // is no more than beta_eps ||T||, or -1.  ||T|| is `an`, the norm over every
+    // step the caller read; on the sharded step that projects by linearity
+    // (mr_step) it is the norm of the steps before i instead.  The launches run
+    // on past a breakdown, on the normalised rounding noise of f, which that
+    // step's projection (exact to eps ||w||, not eps ||f'||) leaves far from
+    // orthogonal to V: beta then grows geometrically from step to step, and
+    // after some twenty such steps (ncv 32 on a star or K_n of 64 nodes) the
+    // norm over all of them had put the threshold above the ||f_1|| of sound
+    // steps, a "breakdown at step 1" that no injected vector could clear.
+    int first_breakdown(int from, int last, double an, const double* fn2v) const {
+        double ap = 1.0;
+        int seen = 0;  // ap covers steps [0, seen): only the steps before the one tested are read
+        for (int i = std::max(from, 1); i <= last; ++i) {
+            for (; seen < i; ++seen) ap = std::max(ap, t_row(seen));
+            if (!(std::sqrt(std::max(0.0, fn2v[i])) > beta_eps * (mr_step ? ap : an))) return i;
+        }
+        return -1;
+    }
+
     // What ends a run of steps before the cycle does.
     struct Found {
         int j1 = -1;          // breakdown at step j1 (||f_j1|| collapsed)
@@ -1059,9 +1081,8 @@ struct Solve {
             if (i > 0) e[size_t(i - 1)] = pa[m + i];
         }
         double an = 1.0;
-        for (int i = 0; i < j; ++i) an = std::max(an, std::fabs(d[size_t(i)]) + (i > 0 ? std::fabs(e[size_t(i - 1)]) : 0.0));
-        for (int i = std::max(from, 1); i <= j && f.j1 < 0; ++i)
-            if (!(std::sqrt(std::max(0.0, pa[2 * m + i])) > beta_eps * an)) f.j1 = i;
+        for (int i = 0; i < j; ++i) an = std::max(an, t_row(i));
+        f.j1 = first_breakdown(from, j, an, pa + 2 * m);
         for (int i = from; mr_step && i < j && f.jr < 0; ++i)
             if (pa[L.CHK_FLAGS + size_t(i)] != 0.0) {
                 f.jr = i + 1;
@@ -1143,12 +1164,7 @@ struct Solve {
             d[size_t(i)] = alpha_h[size_t(i)];
             if (i > 0) e[size_t(i - 1)] = offd_h[size_t(i)];
         }
-        const double an = anorm();
-        for (int i = std::max(from, 1); i < m; ++i)
-            if (!(std::sqrt(std::max(0.0, fn2_h[size_t(i)])) > beta_eps * an)) {
-                f.j1 = i;
-                break;
-            }
+        f.j1 = first_breakdown(from, m - 1, anorm(), fn2_h.data());
         if (mr_step && f.j1 < 0) {
             std::vector<double> cf(static_cast<size_t>(m));
             HIPCHK(hipMemcpyAsync(cf.data(), c->cflag.p, size_t(m) * 8, hipMemcpyDeviceToHost, s));

@@ -155,8 +155,9 @@ void own_build_host(ek_ctx* c, const int32_t* rowptr, const int32_t* col, const 
     }
     c->own_nnz = int64_t(oc.size());
     upload(c->own_rowptr, orp.data(), orp.size(), c->stream);
-    upload(c->own_col, oc.data(), std::max<size_t>(oc.size(), 1), c->stream);
-    upload(c->own_val, ov.data(), std::max<size_t>(ov.size(), 1), c->stream);
+    // (a rank of no rows has no owned entry, and an empty vector no data to copy one from)
+    upload(c->own_col, oc.data(), oc.size(), c->stream);
+    upload(c->own_val, ov.data(), ov.size(), c->stream);
     own_finish(c, orp);
 }
 
@@ -224,7 +225,7 @@ void spmv_setup_rows(ek_ctx* c, int64_t n, const std::vector<int64_t>& off, cons
     // 512-nnz blocks (tools/spmv_lab.hip for plain CSR; for the coded form,
     // 1024-nnz segments measured 14.3 against 12.7 us inside the solve)
     c->pn_G = 0;
-    if (packed && want_panels(c)) {
+    if (packed && nrows > 0 && want_panels(c)) {  // (no rows: no panel workgroups; the one empty row block)
         DBuf rp_d, pk_d;
         upload(c->dict, dictv.data(), dictv.size(), c->stream);
         upload(rp_d, rowptr, size_t(nrows) + 1, c->stream);
@@ -518,7 +519,7 @@ static int spmv_setup_pins_impl(ek_ctx* c, int64_t n, int64_t nets, const int64_
         packed = cnt_h[1] == 0 && nd <= TSIZE / 2 && nd <= (int64_t(1) << (32 - colbits));
     }
     c->pn_G = 0;
-    if (packed && want_panels(c)) {
+    if (packed && nrows > 0 && want_panels(c)) {  // (no rows: no panel workgroups; the one empty row block)
         DBuf pk_d;
         c->dict.ensure(size_t(std::max<int64_t>(ncodes, 1)) * 8);
         ek::dev::dict_values(s, c->lb_table.as<unsigned long long>(), TSIZE, c->lb_codes.as<long long>(),

@@ -28,6 +28,11 @@ std::vector<int32_t> spmv_row_blocks(const int32_t* rowptr, int64_t nrows, int b
         }
     }
     if (starts.back() != int32_t(nrows)) starts.push_back(int32_t(nrows));
+    // A rank that owns no rows (an empty slice of the shard map) still gets one
+    // block, of no rows and no entries: the Lanczos step's SpMV publishes
+    // ||f||^2 and the previous step's alpha / beta from block 0's prologue, on
+    // every rank, so a grid of no blocks would leave that rank's T stale.
+    if (nrows <= 0) return {0, 0, 0, 0};
     // one {row0, nrows, nnz0, cnt} record per block
     std::vector<int32_t> desc;
     desc.reserve((starts.size() - 1) * 4);

@@ -202,7 +202,10 @@ int ek_comm_init_host(ek_ctx* ctx, int nranks, int rank, ek_allgather_fn allgath
  * nrows+1 entries starting at 0; col holds global column ids.  Host arrays
  * are copied; the caller keeps ownership.  Sharded contexts: every rank
  * calls it; the ranks' [row0, row0+nrows) must tile [0, n) in rank order
- * (learned with one all-gather; ek_shard_map or ek_shard_rows). */
+ * (learned with one all-gather; ek_shard_map or ek_shard_rows).  A rank
+ * may own no rows (nrows 0, rowptr = {0}): it takes part in every
+ * collective, and ek_spmv / ek_lanczos_fiedler give it what they give the
+ * other ranks (an empty y; the same pair). */
 int ek_spmv_setup(ek_ctx* ctx, int64_t n, int64_t row0, int64_t nrows, const int32_t* rowptr,
                   const int32_t* col, const double* val);
 /* The same rows built on the GPU straight from the hypergraph's pins (net e

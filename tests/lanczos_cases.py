@@ -144,3 +144,37 @@ class Ref:
 @functools.lru_cache(maxsize=None)
 def reference(name):
     return Ref(name, dense_laplacian(name))
+
+
+def check_pair(ek, name, lam, v, st, what=""):
+    """The solver's pair (lam, v, stats) against the dense-eigensolver reference
+    of `name`, with the bounds of this module (test_gpu_lanczos_small.py and,
+    per rank, test_gpu_mr_small.py)."""
+    ref = reference(name)
+    assert st["converged"], st
+    assert np.all(np.isfinite(v)) and np.isfinite(lam)
+    r = ref.residual(lam, v)
+    b = ref.bound(r)
+    print(f"{name} {what}: {ref.klass}, matvecs {st['matvecs']}, restarts {st['restarts']}, residual {r:.3g}, "
+          f"|lambda - ref| {abs(lam - ref.lam2):.3g} (bound {b:.3g})")
+    if ref.klass == "disconnected":
+        assert r <= 1e-8 and abs(lam) <= 1e-8
+    else:
+        assert r <= 1e-9
+    assert abs(np.linalg.norm(v) - 1) <= 1e-12 and abs(v.sum()) <= 1e-8
+    assert abs(lam - ref.lam2) <= b, (lam, ref.lam2)
+    if ref.w[2] - ref.w[1] > 2 * b:  # the second eigenvalue, not just some eigenvalue
+        assert abs(lam - ref.w[1]) < abs(lam - ref.w[2])
+    if ref.klass == "nondegenerate":
+        v_ref = ref.U[:, 1]
+        v = v * np.sign(v @ v_ref)
+        band = ref.angle(r)
+        assert np.linalg.norm(v - v_ref) <= band, (np.linalg.norm(v - v_ref), band)
+        med_ref, bits_ref = ek.median_split(v_ref)
+        _, bits = ek.median_split(v)
+        mask = ref.outside_band(r, med_ref)
+        print(f"{name} {what}: outside the Davis-Kahan band {int(mask.sum())}/{ref.n} = {mask.mean():.4f}")
+        assert np.array_equal(bits[mask], bits_ref[mask])
+    elif np.isfinite(ref.gap):  # (K_n: every vector orthogonal to 1 is an eigenvector; |sum v| above)
+        off = np.linalg.norm(v - ref.space @ (ref.space.T @ v))
+        assert off <= ref.angle(r), (off, ref.angle(r))

@@ -32,42 +32,11 @@ def _setup(ek, ctx, name):
     return h
 
 
-def _check(ek, name, lam, v, st, what=""):
-    ref = lc.reference(name)
-    assert st["converged"], st
-    assert np.all(np.isfinite(v)) and np.isfinite(lam)
-    r = ref.residual(lam, v)
-    b = ref.bound(r)
-    print(f"{name} {what}: {ref.klass}, matvecs {st['matvecs']}, restarts {st['restarts']}, residual {r:.3g}, "
-          f"|lambda - ref| {abs(lam - ref.lam2):.3g} (bound {b:.3g})")
-    if ref.klass == "disconnected":
-        assert r <= 1e-8 and abs(lam) <= 1e-8
-    else:
-        assert r <= 1e-9
-    assert abs(np.linalg.norm(v) - 1) <= 1e-12 and abs(v.sum()) <= 1e-8
-    assert abs(lam - ref.lam2) <= b, (lam, ref.lam2)
-    if ref.w[2] - ref.w[1] > 2 * b:  # the second eigenvalue, not just some eigenvalue
-        assert abs(lam - ref.w[1]) < abs(lam - ref.w[2])
-    if ref.klass == "nondegenerate":
-        v_ref = ref.U[:, 1]
-        v = v * np.sign(v @ v_ref)
-        band = ref.angle(r)
-        assert np.linalg.norm(v - v_ref) <= band, (np.linalg.norm(v - v_ref), band)
-        med_ref, bits_ref = ek.median_split(v_ref)
-        _, bits = ek.median_split(v)
-        mask = ref.outside_band(r, med_ref)
-        print(f"{name} {what}: outside the Davis-Kahan band {int(mask.sum())}/{ref.n} = {mask.mean():.4f}")
-        assert np.array_equal(bits[mask], bits_ref[mask])
-    elif np.isfinite(ref.gap):  # (K_n: every vector orthogonal to 1 is an eigenvector; |sum v| above)
-        off = np.linalg.norm(v - ref.space @ (ref.space.T @ v))
-        assert off <= ref.angle(r), (off, ref.angle(r))
-
-
 @pytest.mark.parametrize("name", lc.NAMES)
 def test_fiedler_pair_against_dense_eigensolver(ek, ctx, name):
     _setup(ek, ctx, name)
     lam, v, st = ctx.lanczos_fiedler()
-    _check(ek, name, lam, v, st, "default")
+    lc.check_pair(ek, name, lam, v, st, "default")
     lam2, v2, st2 = ctx.lanczos_fiedler()  # the same bits on the resident matrix
     assert lam == lam2 and np.array_equal(v.view(np.uint64), v2.view(np.uint64)) and st["matvecs"] == st2["matvecs"]
 
@@ -89,4 +58,4 @@ def test_fiedler_pair_modes(ek, ctx, name, mode):
         assert e.value.code == ek.EK_EINVAL
         return
     lam, v, st = ctx.lanczos_fiedler(**mode)
-    _check(ek, name, lam, v, st, _mode_id(mode))
+    lc.check_pair(ek, name, lam, v, st, _mode_id(mode))
