@@ -126,6 +126,19 @@ class KwayRefineWResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in _REFINE_TIMES])
 
 
+class KwayJetOpts(_AbiStruct):
+    _fields_ = [("k", _I32), ("max_iters", _I32), ("patience", _I32), ("neg_num", _I32), ("neg_den", _I32),
+                ("pad", _I32), ("imbalance", ctypes.c_double)]
+
+
+class KwayJetResult(_AbiStruct):
+    _fields_ = ([("k", _I32), ("iters", _I32), ("best_iter", _I32), ("pad", _I32)]
+                + [(k, _I64) for k in ("moves", "total_weight", "bound_min", "bound_max", "connectivity_w_before",
+                                       "cut_nets", "connectivity", "connectivity_w", "soed", "part_w_min",
+                                       "part_w_max", "parts_over_bound")]
+                + [(k, ctypes.c_double) for k in ("t_setup", "t_iters", "t_metrics")])
+
+
 class SweepOpts(_AbiStruct):
     _fields_ = [("objective", _I32), ("pad", _I32), ("imbalance", ctypes.c_double)]
 
@@ -350,6 +363,11 @@ _sig("ek_kway_refine_w_host", ctypes.c_int, _P, ctypes.POINTER(KwayRefineOpts), 
      ctypes.POINTER(KwayRefineWResult))
 _sig("ek_kway_refine_w", ctypes.c_int, _P, _P, ctypes.POINTER(KwayRefineOpts), _P, _P, _P, _I64,
      ctypes.POINTER(KwayRefineWResult))
+_sig("ek_kway_jet_default_opts", None, ctypes.POINTER(KwayJetOpts))
+_sig("ek_kway_jet_host", ctypes.c_int, _P, ctypes.POINTER(KwayJetOpts), _P, _P, _P, _I64,
+     ctypes.POINTER(KwayJetResult))
+_sig("ek_kway_jet", ctypes.c_int, _P, _P, ctypes.POINTER(KwayJetOpts), _P, _P, _P, _I64,
+     ctypes.POINTER(KwayJetResult))
 _sig("ek_sweep_default_opts", None, ctypes.POINTER(SweepOpts))
 _sig("ek_sweep_cut_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
 _sig("ek_sweep_cut", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
@@ -718,6 +736,42 @@ def kway_refine_w_host(hgr, part, k, imbalance=0.03, max_rounds=0, bounds=None):
     bounds is None, its net weights in the connectivity.  Returns (part, result dict, round log)."""
     return _kway_refine_w(lambda *a: _lib.ek_kway_refine_w_host(hgr._h, *a), "kway_refine_w_host", hgr, part, k,
                           imbalance, max_rounds, bounds)
+
+
+def _kway_jet(call, what, hgr, part, k, imbalance, bounds, max_iters, patience, neg):
+    """_kway_refine_w for the Jet entries: neg is the negative-gain filter (neg_num, neg_den)."""
+    start = np.ascontiguousarray(part, np.int32)
+    if len(start) != hgr.nodes:
+        raise ValueError(f"part has {len(start)} entries for {hgr.nodes} nodes")
+    if bounds is not None:
+        bounds = np.ascontiguousarray(bounds, np.int64)
+        if len(bounds) != int(k):
+            raise ValueError(f"{len(bounds)} bounds for {k} parts")
+    o = KwayJetOpts()
+    _lib.ek_kway_jet_default_opts(ctypes.byref(o))
+    o.k, o.max_iters, o.patience, o.imbalance = int(k), int(max_iters), int(patience), float(imbalance)
+    o.neg_num, o.neg_den = int(neg[0]), int(neg[1])
+    cap = int(max_iters) if max_iters > 0 else 256
+    while True:
+        out = start.copy()
+        log = np.zeros((cap, 4), np.int64)
+        r = KwayJetResult()
+        _chk(call(ctypes.byref(o), _p(bounds), _p(out), _p(log), cap, ctypes.byref(r)), what)
+        if r.iters <= cap:  # (else: deterministic, so the same run again with room for its log)
+            break
+        cap = r.iters
+    res = {name: getattr(r, name) for name, _ in KwayJetResult._fields_ if name != "pad"}
+    return out, res, log[:r.iters].copy()
+
+
+def kway_jet_host(hgr, part, k, eps=0.03, bounds=None, max_iters=0, patience=12, neg=(1, 4)):
+    """Parallel weighted k-way refinement that can leave a local minimum (the Jet rule on the weighted connectivity),
+    on the host (ek_kway_jet_host, the device path's checker): hgr's node weights under bounds[p], or under
+    floor((1 + eps) ceil(W / k)) when bounds is None.  Returns (part, result dict, iteration log); a log row is
+    (candidates, passing candidates, accepted moves, the weighted connectivity after the iteration), and part is
+    the best state seen."""
+    return _kway_jet(lambda *a: _lib.ek_kway_jet_host(hgr._h, *a), "kway_jet_host", hgr, part, k, eps, bounds,
+                     max_iters, patience, neg)
 
 
 def _sweep_opts(imbalance, ratio):
@@ -1340,6 +1394,12 @@ class Context:
         round log.  Returns (part, result dict, round log)."""
         return _kway_refine_w(lambda *a: _lib.ek_kway_refine_w(self._c, hgr._h, *a), "kway_refine_w", hgr, part, k,
                               imbalance, max_rounds, bounds)
+
+    def kway_jet(self, hgr, part, k, eps=0.03, bounds=None, max_iters=0, patience=12, neg=(1, 4)):
+        """kway_jet_host on the GPU (ek_kway_jet): the same part vector, result integers and iteration
+        log.  Returns (part, result dict, iteration log)."""
+        return _kway_jet(lambda *a: _lib.ek_kway_jet(self._c, hgr._h, *a), "kway_jet", hgr, part, k, eps, bounds,
+                         max_iters, patience, neg)
 
     def match(self, hgr, max_cluster=2, max_net=64, max_rounds=8):
         """match_host on the GPU (ek_match): the same mate, cluster, round log and result integers."""

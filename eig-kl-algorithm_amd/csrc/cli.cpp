@@ -86,6 +86,13 @@
 //                        the refined vector is what results/<base>.part.<N>
 //                        holds, and one more line beginning "refine-w:" is
 //                        printed
+//   --refine-jet EPS2    with --kway-multilevel: then the Jet refinement on the
+//                        device (ek_kway_jet, defaults: patience 12, filter 1/4)
+//                        on the same reading of the file, under the uniform
+//                        bound floor((1 + EPS2) ceil(W / N)); --jet-iters I
+//                        limits its iterations; excludes --refine-weighted; the
+//                        refined vector is what results/<base>.part.<N> holds,
+//                        and one more line beginning "refine-jet:" is printed
 //   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
 //                        carries its net weights (EK_ML_WEIGHTED_LAPLACIAN,
 //                        -(2 c(e) / |e|) per pin pair); the "ml:" line ends
@@ -150,6 +157,11 @@ int kway_ml_refine_w_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek
                                   int coarse_nodes, int max_passes, int stall, int32_t flags, double refine_imbalance,
                                   int max_rounds, ek_kway_ml_result* mr, ek_kway_refine_w_result* rr)
     __attribute__((weak));
+// kway_jet.cpp: the same with ek_kway_jet in place of ek_kway_refine_w, for
+// `--k N --kway-multilevel EPS --refine-jet EPS2`
+int kway_ml_jet_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                             int coarse_nodes, int max_passes, int stall, int32_t flags, double jet_imbalance,
+                             int max_iters, ek_kway_ml_result* mr, ek_kway_jet_result* jr) __attribute__((weak));
 }
 
 namespace {
@@ -174,6 +186,9 @@ struct Opts {
     bool kml = false;                 // --kway-multilevel EPS (sets ml and ml_eps too): with --k, the k-way driver
     bool refine_w = false;            // --refine-weighted EPS2 (with --kway-multilevel)
     double refine_w_eps = 0.0;
+    bool jet = false, jet_sub = false;  // --refine-jet EPS2 (with --kway-multilevel); --jet-iters seen
+    double jet_eps = 0.0;
+    int jet_iters = 0;  // --jet-iters I (0: no limit)
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -487,6 +502,9 @@ constexpr const char* ML_USAGE =
     "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> --refine-weighted <imbalance> "
     "[--refine-rounds <R>]  (then the weighted k-way refinement under floor((1 + imbalance) ceil(W / parts)); needs "
     "--kway-multilevel; the refine-w: line follows)\n"
+    "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> --refine-jet <imbalance> "
+    "[--jet-iters <I>]  (then the Jet refinement under floor((1 + imbalance) ceil(W / parts)); needs "
+    "--kway-multilevel, excludes --refine-weighted; the refine-jet: line follows)\n"
     "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> --ml-weighted-laplacian  (the coarsest level's Laplacian "
     "carries its net weights, -(2 c(e) / |e|) per pin pair; needs --multilevel; the ml: line ends with wlap=1)\n";
 
@@ -519,7 +537,14 @@ int run_kway_ml(const Opts& o) {
     if (!ek::kway_ml_file_for_cli) throw Fail{"this build carries no multilevel k-way path"};
     ek_kway_ml_result r{};
     ek_kway_refine_w_result rr{};
-    if (o.refine_w) {
+    ek_kway_jet_result jr{};
+    if (o.jet) {
+        if (!ek::kway_ml_jet_file_for_cli) throw Fail{"this build carries no Jet refinement"};
+        check(ek::kway_ml_jet_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse,
+                                           o.fm_passes, o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0, o.jet_eps,
+                                           o.jet_iters, &r, &jr),
+              "multilevel k-way partition and Jet refinement");
+    } else if (o.refine_w) {
         if (!ek::kway_ml_refine_w_file_for_cli) throw Fail{"this build carries no weighted k-way refinement"};
         check(ek::kway_ml_refine_w_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse,
                                                 o.fm_passes, o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0,
@@ -546,6 +571,13 @@ int run_kway_ml(const Opts& o) {
                     rr.rounds, (long long)rr.moves, (long long)rr.connectivity_w_before, (long long)rr.connectivity_w,
                     (long long)rr.cut_nets, (long long)rr.part_w_min, (long long)rr.part_w_max,
                     (long long)rr.parts_over_bound, rr.t_setup + rr.t_rounds + rr.t_metrics);
+    if (o.jet)
+        std::printf("refine-jet: imbalance %g (bound %lld), %d iterations, best %d, %lld moves, connectivity_w %lld -> "
+                    "%lld, cut nets %lld, part weights %lld..%lld, over_bound %lld, %.3f s\n", o.jet_eps,
+                    (long long)jr.bound_max, jr.iters, jr.best_iter, (long long)jr.moves,
+                    (long long)jr.connectivity_w_before, (long long)jr.connectivity_w, (long long)jr.cut_nets,
+                    (long long)jr.part_w_min, (long long)jr.part_w_max, (long long)jr.parts_over_bound,
+                    jr.t_setup + jr.t_iters + jr.t_metrics);
     return 0;
 }
 
@@ -591,6 +623,14 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.refine_w_eps = std::stod(need("--refine-weighted"));
                 if (!std::isfinite(o.refine_w_eps) || o.refine_w_eps < 0)
                     throw Fail{"--refine-weighted takes an imbalance >= 0"};
+            }
+            else if (a == "--refine-jet") {
+                o.jet = true;  // (before the value, as --refine-weighted)
+                o.jet_eps = std::stod(need("--refine-jet"));
+                if (!std::isfinite(o.jet_eps) || o.jet_eps < 0) throw Fail{"--refine-jet takes an imbalance >= 0"};
+            } else if (a == "--jet-iters") {
+                o.jet_sub = true;
+                o.jet_iters = std::stoi(need("--jet-iters"));
             }
             else if (a == "--sweep") {
                 o.sweep_eps = std::stod(need("--sweep"));
@@ -638,17 +678,26 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
         } catch (const Fail& e) {
             std::fprintf(stderr, "Error: %s\n", e.msg.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
-            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted") std::printf("%s", ML_USAGE);
+            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
+                a == "--jet-iters")
+                std::printf("%s", ML_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
-            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted") std::printf("%s", ML_USAGE);
+            if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
+                a == "--jet-iters")
+                std::printf("%s", ML_USAGE);
             return 1;
         }
     }
     try {
         if (o.refine_w && !o.kml) {  // --refine-weighted follows --kway-multilevel only
+            std::printf("%s", ML_USAGE);
+            return 1;
+        }
+        // --refine-jet follows --kway-multilevel only and stands in place of --refine-weighted; --jet-iters needs it
+        if ((o.jet || o.jet_sub) && (!o.jet || !o.kml || o.refine_w)) {
             std::printf("%s", ML_USAGE);
             return 1;
         }

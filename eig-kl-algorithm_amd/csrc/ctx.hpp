@@ -6,7 +6,7 @@
 //   ctx_comm.cpp     collectives and their timing, shard map, halo exchange
 //   ctx_spmv.cpp     SpMV set-up (host rows / device Laplacian build), ek_spmv*
 //   ctx_lanczos.cpp  the implicitly restarted Lanczos, ek_lanczos_fiedler
-//   ctx_kl.cpp, ctx_kway.cpp, ctx_kway_refine_w.cpp, ctx_sweep.cpp, ctx_fm.cpp   the partition drivers
+//   ctx_kl.cpp, ctx_kway.cpp, ctx_kway_refine_w.cpp, ctx_kway_jet.cpp, ctx_sweep.cpp, ctx_fm.cpp   the partition drivers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

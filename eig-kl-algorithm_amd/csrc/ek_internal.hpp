@@ -257,6 +257,13 @@ struct RefineWInput : WeightedInput {
 void refine_w_prepare(const char* who, const ek_hgr* h, const ek_kway_refine_opts* opts, const int64_t* bounds,
                       const int32_t* part, RefineWInput& out);
 
+// kway_jet.cpp — what the host and the device Jet refinement (§18) share: the
+// input.  refine_w_prepare under k and the imbalance of the Jet opts, and the
+// new options' checks (neg_num >= 0, neg_den >= 1, patience >= 1, EK_EINVAL
+// otherwise); returns the opts with the defaults filled in
+ek_kway_jet_opts jet_prepare(const char* who, const ek_hgr* h, const ek_kway_jet_opts* opts, const int64_t* bounds,
+                             const int32_t* part, RefineWInput& out);
+
 // match.cpp — what the host and the device matching share: the argument checks
 // (EK_EINVAL as eigkl.h lists it; the opts with the defaults filled in) and the
 // input, weights_prepare's
@@ -845,6 +852,23 @@ struct RefineWDev {
 };
 // slot as refine_round's.  nets > 0.
 void refine_w_round(hipStream_t s, const RefineWDev& d, unsigned long long* slot);
+// k_refine_w_select by itself, with refine_w_round's grid, for the Jet
+// iteration (kernels_jet.hip): thr[b] of every part b < k from the list of
+// slot[1] unique keys with ~id in the low word
+void refine_w_select(hipStream_t s, int k, const unsigned long long* list, const uint8_t* tgt, const int32_t* w,
+                     const long long* S, const long long* L, const unsigned long long* slot, unsigned long long* thr);
+
+// kernels_jet.hip — one iteration of the Jet refinement (ek_kway_jet, §18)
+// up to its moves: RefineWDev's arrays (win unused) and the two lock arrays
+struct JetDev {
+    RefineWDev r;
+    int neg_num, neg_den;
+    const uint8_t* lock;  // n: 1 for the nodes that moved in the iteration before
+    uint8_t* lock_next;   // n, zero before: gets 1 for the nodes this one moves
+};
+// slot (device, zero before the iteration): the iteration's candidates,
+// passing candidates and accepted moves (slot[3] is left alone).  nets > 0.
+void jet_iteration(hipStream_t s, const JetDev& d, unsigned long long* slot);
 
 // kernels_sweep.hip — the sweep cuts (ek_sweep_cut, ek_sweep_cut_w): sort,
 // scans, the count and the weighted profile, prefix weights, the two choices

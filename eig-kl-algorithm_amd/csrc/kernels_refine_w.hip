@@ -242,5 +242,12 @@ void refine_w_round(hipStream_t s, const RefineWDev& d, u64* slot) {
                        reinterpret_cast<u64*>(d.S), slot);
 }
 
+// The select by itself, with refine_w_round's grid: the Jet iteration
+// (kernels_jet.hip) puts it between its own afterburner and apply kernels.
+void refine_w_select(hipStream_t s, int k, const u64* list, const uint8_t* tgt, const int32_t* w, const long long* S,
+                     const long long* L, const u64* slot, u64* thr) {
+    hipLaunchKernelGGL(k_refine_w_select, dim3(unsigned(k)), dim3(RW_THREADS), 0, s, list, tgt, w, S, L, slot, thr);
+}
+
 }  // namespace dev
 }  // namespace ek

@@ -80,7 +80,7 @@ void ek_hgr_free(ek_hgr* h);
  * ones.  Only the weighted FM refinement, the weighted sweep cut
  * (ek_sweep_cut_w*), the matching, the multilevel paths over them
  * (ek_multilevel_bipartition*, ek_partition_kway_ml), the weighted k-way
- * refinement (ek_kway_refine_w*) and the weighted metrics read them: the Laplacian, the KL graph, the Lanczos solve, the median, rank
+ * refinements (ek_kway_refine_w*, ek_kway_jet*) and the weighted metrics read them: the Laplacian, the KL graph, the Lanczos solve, the median, rank
  * and count-sweep splits, KL, ek_partition_kway, ek_kway_refine and
  * ek_fm_refine work on the structure alone.  ek_hgr_write writes a
  * weighted hypergraph in the hMETIS form below (fmt, the net weights, the node
@@ -1196,6 +1196,81 @@ int ek_kway_refine_w_host(const ek_hgr* h, const ek_kway_refine_opts* opts, cons
  * to the call. */
 int ek_kway_refine_w(ek_ctx* ctx, const ek_hgr* h, const ek_kway_refine_opts* opts, const int64_t* bounds,
                      int32_t* part_inout, int64_t* round_log, int64_t log_rounds, ek_kway_refine_w_result* result);
+
+/* ------------------------------------------------------------------ */
+/* Parallel weighted k-way refinement that can leave a local minimum    */
+/* (the Jet rule on the connectivity metric).  No reference counterpart. */
+/* ------------------------------------------------------------------ */
+/* Input, weights, S(p) and the bounds L_p exactly as ek_kway_refine_w
+ * (DESIGN.md §18).  State: the part vector, S and one lock per node, all clear
+ * at the start.  Everything is integer, ties are broken by ids, and iteration
+ * i = 1, 2, ... reads only the state at its start:
+ *  (a) for an unlocked v on at least one net, a = part(v): r(v), c(v,b) and
+ *      g(v,b) = (r - D) + c(v,b) as ek_kway_refine_w's (a).  The target t(v) is
+ *      the open part (S(b) + w(v) <= L_b, b != a) of greatest g, ties to the
+ *      smaller b, WHATEVER THE SIGN of g.  v is a candidate iff it has an open
+ *      part and either g >= 0 or -g neg_den < neg_num (D(v) - r(v)), in int64.
+ *      Its key is K(v) = ((g + 2^31) << 32) | ~id: never 0, unique, ordered by
+ *      (g descending, id ascending);
+ *  (b) the afterburner: for a candidate v and a pin u != v of one of its nets,
+ *      p'(u) = t(u) if u is a candidate with K(u) > K(v), else part(u);
+ *      g'(v) = the sum over v's nets e of c(e) ([no u in e \ {v} has p'(u) = a]
+ *      - [no u in e \ {v} has p'(u) = t(v)]); v passes iff g'(v) >= 0.  A
+ *      better-ranked candidate counts as moved whether or not it passes;
+ *  (c) per part b the passing candidates with target b in K-descending order;
+ *      the accepted set is the longest prefix whose summed w is at most L_b -
+ *      S(b), ek_kway_refine_w's (c) word for word;
+ *  (d) accepted nodes move; exactly they are locked during iteration i + 1;
+ *  (e) X_i is the weighted connectivity recounted after the moves (accepted
+ *      nodes may share nets, so it is not X_{i-1} minus the gains); X_0 is the
+ *      start's.  If X_i < best (strictly): best = X_i, best_iter = i, the part
+ *      vector is kept as the snapshot and since = 0; otherwise ++since;
+ *  (f) stop after iteration i when since == patience, or i == max_iters (when
+ *      > 0), or iterations i and i - 1 both accepted nothing ("iteration 0"
+ *      accepted nothing): no node is locked then and i + 1 would repeat i.
+ * With no net of 2 distinct pins the call returns at once (0 iterations).  The
+ * result is the SNAPSHOT, the start itself when nothing improved, and the
+ * result's part weights and metrics are recounted from it.  Its weighted
+ * connectivity is at most the start's; no part ends above max(L_p, its initial
+ * S(p)); a single iteration may raise the objective. */
+typedef struct {
+    int32_t k;         /* number of parts, 2..256 */
+    int32_t max_iters; /* <= 0: none */
+    int32_t patience;  /* iterations without a new best before the stop, >= 1; default 12 */
+    int32_t neg_num;   /* the negative-gain filter neg_num / neg_den: >= 0, default 1 */
+    int32_t neg_den;   /* >= 1, default 4 */
+    int32_t pad;
+    double imbalance;  /* epsilon >= 0 of the uniform bound; default 0.03; ignored with bounds */
+} ek_kway_jet_opts;
+void ek_kway_jet_default_opts(ek_kway_jet_opts* opts);
+
+typedef struct {
+    int32_t k, iters, best_iter, pad;      /* iterations run; the one the result is the state after (0: the start) */
+    int64_t moves;                         /* accepted moves over all iterations, those rolled back among them */
+    int64_t total_weight;                  /* W */
+    int64_t bound_min, bound_max;          /* least / greatest L_p as used */
+    int64_t connectivity_w_before;         /* X_0 */
+    int64_t cut_nets, connectivity, connectivity_w, soed; /* ek_kway_metrics_w of the result */
+    int64_t part_w_min, part_w_max;        /* of the result */
+    int64_t parts_over_bound;              /* parts of the result with S(p) > L_p */
+    double t_setup, t_iters, t_metrics;    /* wall seconds (host clock) */
+} ek_kway_jet_result;
+
+/* The refinement on the host (no GPU): the checker of ek_kway_jet, single
+ * threaded and written from the rule.  part_inout: the start on entry, the
+ * snapshot on return.  iter_log (may be NULL) gets four values per iteration,
+ * for the first log_iters iterations: candidates, passing candidates, accepted
+ * moves and X_i; every iteration that ran is logged, the last included.
+ * EK_EINVAL as ek_kway_refine_w_host, plus neg_num < 0, neg_den < 1 and
+ * patience < 1. */
+int ek_kway_jet_host(const ek_hgr* h, const ek_kway_jet_opts* opts, const int64_t* bounds /* k, or NULL */,
+                     int32_t* part_inout, int64_t* iter_log, int64_t log_iters, ek_kway_jet_result* result);
+/* The same on the GPU: the same part vector, iteration log and result integers.
+ * Six launches an iteration; the host reads one 64-byte record per iteration.
+ * EK_ESTATE on a multi-rank context.  Keeps nothing on the context: every
+ * buffer is local to the call. */
+int ek_kway_jet(ek_ctx* ctx, const ek_hgr* h, const ek_kway_jet_opts* opts, const int64_t* bounds,
+                int32_t* part_inout, int64_t* iter_log, int64_t log_iters, ek_kway_jet_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
