@@ -251,6 +251,36 @@ class KwayMlResult(_AbiStruct):
                 + [("t_level", ctypes.c_double * KWAY_LEVELS)])
 
 
+class ContractOpts(_AbiStruct):
+    """eigkl.h ek_contract_opts."""
+    _fields_ = [("hash_bits", _I32), ("pad", _I32)]
+
+
+KWAY_DIRECT_HOST_CONTRACT = 1  # eigkl.h EK_KWAY_DIRECT_HOST_CONTRACT
+KWAY_DIRECT_WEIGHTED_LAPLACIAN = 2  # eigkl.h EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN
+
+
+class KwayDirectOpts(_AbiStruct):
+    """eigkl.h ek_kway_direct_opts."""
+    _fields_ = [("k", _I32), ("flags", _I32), ("imbalance", ctypes.c_double), ("coarse_nodes", _I32),
+                ("max_levels", _I32), ("match", MatchOpts), ("initial", KwayMlOpts), ("jet", KwayJetOpts),
+                ("write_results", _I32), ("pad", _I32), ("out_dir", ctypes.c_char_p)]
+
+
+_KWAY_DIRECT_LEVEL_FIELDS = ("nodes", "nets", "pins", "match_rounds", "match_pairs", "conn_w_before", "conn_w_after",
+                             "jet_iters", "jet_moves")
+_KWAY_DIRECT_INTS = ("total_weight", "part_bound", "max_cluster", "part_w_min", "part_w_max", "parts_over_bound",
+                     "empty_parts", "cut_nets", "connectivity", "connectivity_w", "soed")
+_KWAY_DIRECT_TIMES = ("t_match", "t_contract", "t_initial", "t_jet", "t_metrics", "t_total")
+
+
+class KwayDirectResult(_AbiStruct):
+    """eigkl.h ek_kway_direct_result."""
+    _fields_ = ([("k", _I32), ("levels", _I32), ("initial_fallbacks", _I32), ("infeasible_sweeps", _I32)]
+                + [(k, _I64 * (ML_LEVELS + 1)) for k in _KWAY_DIRECT_LEVEL_FIELDS]
+                + [(k, _I64) for k in _KWAY_DIRECT_INTS] + [(k, ctypes.c_double) for k in _KWAY_DIRECT_TIMES])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -417,6 +447,13 @@ _sig("ek_kway_ml_default_opts", None, ctypes.POINTER(KwayMlOpts))
 _sig("ek_partition_kway_ml", ctypes.c_int, _P, _P, ctypes.POINTER(KwayMlOpts), _P, ctypes.POINTER(KwayMlResult))
 _sig("ek_partition_kway_ml_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayMlOpts), _P,
      ctypes.POINTER(KwayMlResult))
+_sig("ek_contract_default_opts", None, ctypes.POINTER(ContractOpts))
+_sig("ek_hgr_contract_device", ctypes.c_int, _P, _P, _P, _I64, ctypes.POINTER(ContractOpts), ctypes.POINTER(_P))
+_sig("ek_kway_direct_default_opts", None, ctypes.POINTER(KwayDirectOpts))
+_sig("ek_partition_kway_direct", ctypes.c_int, _P, _P, ctypes.POINTER(KwayDirectOpts), _P,
+     ctypes.POINTER(KwayDirectResult))
+_sig("ek_partition_kway_direct_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayDirectOpts), _P,
+     ctypes.POINTER(KwayDirectResult))
 
 lib = _lib
 
@@ -895,6 +932,35 @@ def _kway_ml_result(r):
     return out
 
 
+def _kway_direct_opts(k, eps, host_contract, weighted_laplacian, coarse_nodes, jet, initial, write_results, out_dir):
+    """jet: ek_kway_jet_opts fields to override (max_iters, patience, neg_num, neg_den); initial: ek_ml_opts fields of
+    the initial partition to override, `fm`, `match` and `lanczos` as dicts of their own fields."""
+    o = KwayDirectOpts()
+    _lib.ek_kway_direct_default_opts(ctypes.byref(o))
+    o.k, o.imbalance, o.coarse_nodes = int(k), float(eps), int(coarse_nodes)
+    o.flags = ((KWAY_DIRECT_HOST_CONTRACT if host_contract else 0)
+               | (KWAY_DIRECT_WEIGHTED_LAPLACIAN if weighted_laplacian else 0))
+    o.write_results = 1 if write_results else 0
+    o.out_dir = os.fsencode(out_dir) if out_dir else None
+    for name, val in (jet or {}).items():
+        setattr(o.jet, name, val)
+    for name, val in (initial or {}).items():
+        if isinstance(val, dict):
+            for sub, x in val.items():
+                setattr(getattr(o.initial.ml, name), sub, x)
+        else:
+            setattr(o.initial.ml, name, val)
+    return o
+
+
+def _kway_direct_result(r):
+    out = {k: getattr(r, k) for k in ("k", "levels", "initial_fallbacks", "infeasible_sweeps") + _KWAY_DIRECT_INTS
+           + _KWAY_DIRECT_TIMES}
+    for k in _KWAY_DIRECT_LEVEL_FIELDS:
+        out[k] = list(getattr(r, k))[:r.levels + 1]
+    return out
+
+
 def _fm_refine(call, what, hgr, side, imbalance, max_passes, stall, move_cap, result_type=None):
     """(side, pass_log, move_log, result dict): pass_log has one row per pass run, the last uncounted one
     included, (moves tried, t*, cut, |s0 - s1|); move_log (FM_MOVE_DTYPE) every move tried, in order.
@@ -1330,6 +1396,48 @@ class Context:
         r = KwayMlResult()
         _chk(_lib.ek_partition_kway_ml(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)), "partition_kway_ml")
         return part, _kway_ml_result(r)
+
+    def hgr_contract(self, hgr, cluster, n_coarse=None, hash_bits=64):
+        """Hypergraph.contract on the GPU (ek_hgr_contract_device): the same hypergraph byte for byte.  hash_bits:
+        the low bits of the nets' set signature that group them (1..64); the result does not depend on it."""
+        cluster = np.ascontiguousarray(cluster, np.int32)
+        if len(cluster) != hgr.nodes:
+            raise ValueError(f"cluster has {len(cluster)} entries for {hgr.nodes} nodes")
+        if n_coarse is None:
+            n_coarse = int(cluster.max()) + 1 if len(cluster) else 0
+        o = ContractOpts()
+        _lib.ek_contract_default_opts(ctypes.byref(o))
+        o.hash_bits = int(hash_bits)
+        c = _P()
+        _chk(_lib.ek_hgr_contract_device(self._c, hgr._h, _p(cluster), int(n_coarse), ctypes.byref(o), ctypes.byref(c)),
+             "hgr_contract")
+        return Hypergraph(c)
+
+    def partition_kway_direct(self, hgr, k, eps=0.03, host_contract=False, weighted_laplacian=False, coarse_nodes=0,
+                              jet=None, initial=None):
+        """The direct k-way multilevel partition (ek_partition_kway_direct): one coarsening by matching and
+        contraction (on the device; host_contract: on the host, the same hypergraphs), partition_kway_ml of the
+        coarsest level, then kway_jet at every level on the way back up, all under floor((1 + eps) ceil(W / k)).
+        coarse_nodes 0: max(512, 128 k).  jet / initial: option fields to override (see _kway_direct_opts).  Returns
+        (part id per node, result dict)."""
+        o = _kway_direct_opts(k, eps, host_contract, weighted_laplacian, coarse_nodes, jet, initial, False, None)
+        part = np.full(hgr.nodes, -1, np.int32)
+        r = KwayDirectResult()
+        _chk(_lib.ek_partition_kway_direct(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)),
+             "partition_kway_direct")
+        return part, _kway_direct_result(r)
+
+    def partition_kway_direct_file(self, path, k, eps=0.03, host_contract=False, weighted_laplacian=False,
+                                   coarse_nodes=0, jet=None, initial=None, write_results=True, out_dir=None):
+        """The same on the hMETIS reading of a file; write_results: results/<base>.part.<k> under out_dir
+        (ek_partition_kway_direct_file).  Returns (part id per node, result dict)."""
+        o = _kway_direct_opts(k, eps, host_contract, weighted_laplacian, coarse_nodes, jet, initial, write_results,
+                              out_dir)
+        part = np.full(Hypergraph.read_weighted(path).nodes, -1, np.int32)
+        r = KwayDirectResult()
+        _chk(_lib.ek_partition_kway_direct_file(self._c, os.fsencode(path), ctypes.byref(o), _p(part), ctypes.byref(r)),
+             f"partition_kway_direct_file {path}")
+        return part, _kway_direct_result(r)
 
     def partition_kway_ml_file(self, path, k, imbalance=0.03, coarse_nodes=512, weighted_laplacian=False,
                                write_results=True, out_dir=None, max_passes=0, stall=1000, lanczos=None):

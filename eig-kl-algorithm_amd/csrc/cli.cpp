@@ -93,6 +93,15 @@
 //                        limits its iterations; excludes --refine-weighted; the
 //                        refined vector is what results/<base>.part.<N> holds,
 //                        and one more line beginning "refine-jet:" is printed
+//   --kway-direct EPS    gKL2 <in.hgr> -EIG --k N only: the direct k-way
+//                        multilevel partition (ek_partition_kway_direct_file) with
+//                        imbalance EPS, on the hMETIS reading of the file: one
+//                        coarsening, the recursive driver on the coarsest level,
+//                        the Jet refinement at every level; --ml-coarse N,
+//                        --jet-iters I and --ml-weighted-laplacian apply;
+//                        --contract-host contracts on the host; excludes every
+//                        other partitioner and refinement flag; one line
+//                        beginning "kway-direct:", results/<base>.part.<N>
 //   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
 //                        carries its net weights (EK_ML_WEIGHTED_LAPLACIAN,
 //                        -(2 c(e) / |e|) per pin pair); the "ml:" line ends
@@ -162,6 +171,11 @@ int kway_ml_refine_w_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek
 int kway_ml_jet_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
                              int coarse_nodes, int max_passes, int stall, int32_t flags, double jet_imbalance,
                              int max_iters, ek_kway_ml_result* mr, ek_kway_jet_result* jr) __attribute__((weak));
+// kway_direct.cpp: ek_partition_kway_direct_file with the results file on, for `--k N --kway-direct EPS`
+// (coarse_nodes <= 0, max_iters <= 0: the defaults)
+int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                             int coarse_nodes, int max_iters, int32_t flags, ek_kway_direct_result* r)
+    __attribute__((weak));
 }
 
 namespace {
@@ -189,6 +203,8 @@ struct Opts {
     bool jet = false, jet_sub = false;  // --refine-jet EPS2 (with --kway-multilevel); --jet-iters seen
     double jet_eps = 0.0;
     int jet_iters = 0;  // --jet-iters I (0: no limit)
+    bool kd = false, kd_host = false;  // --kway-direct EPS (with --k); --contract-host (with --kway-direct)
+    double kd_eps = 0.0;
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -581,6 +597,43 @@ int run_kway_ml(const Opts& o) {
     return 0;
 }
 
+constexpr const char* KD_USAGE =
+    "Usage: gKL2 <input_file> -EIG --k <parts> --kway-direct <imbalance> [--ml-coarse <N>] [--jet-iters <I>] "
+    "[--contract-host] [--ml-weighted-laplacian]  (the direct k-way multilevel partition: one coarsening, the Jet "
+    "refinement at every level; needs --k with 2 <= parts <= 256 and an imbalance >= 0; excludes --kway-multilevel, "
+    "--multilevel, --refine, --refine-weighted, --refine-jet, --sweep and --fm; --contract-host contracts on the host; "
+    "the file is read as hMETIS reads it)\n";
+
+// gKL2 <in.hgr> -EIG --k N --kway-direct EPS: one summary line beginning "kway-direct:", results/<base>.part.<N>
+int run_kway_direct(const Opts& o) {
+    const auto t0 = clk::now();
+    CtxInit ci(o.device, o.teardown);
+    const ek_solve_opts so = solve_opts(o);
+    if (!ek::kway_direct_file_for_cli) throw Fail{"this build carries no direct k-way path"};
+    ek_kway_direct_result r{};
+    const int32_t flags = (o.kd_host ? EK_KWAY_DIRECT_HOST_CONTRACT : 0) | (o.ml_wlap ? EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN : 0);
+    check(ek::kway_direct_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.kd_eps, o.ml_coarse, o.jet_iters,
+                                       flags, &r),
+          "direct k-way partition");
+    long long iters = 0, moves = 0;
+    for (int l = 0; l <= r.levels; ++l) {
+        iters += r.jet_iters[l];
+        moves += r.jet_moves[l];
+    }
+    std::printf("kway-direct: k %d, imbalance %g, levels %d, coarsest_nodes %lld, max_cluster %lld, fallbacks %d, "
+                "infeasible %d, total_weight %lld, part_bound %lld, part weights %lld..%lld, over_bound %lld, empty %lld, "
+                "cut nets %lld, connectivity %lld, connectivity_w %lld (initial %lld), SOED %lld, jet iterations %lld, "
+                "jet moves %lld, contract %s, %.3f s (match %.3f, contract %.3f, initial %.3f, jet %.3f, metrics %.3f), "
+                "%.3f s -> results/%s.part.%d%s\n", r.k, o.kd_eps, r.levels, (long long)r.nodes[r.levels],
+                (long long)r.max_cluster, r.initial_fallbacks, r.infeasible_sweeps, (long long)r.total_weight,
+                (long long)r.part_bound, (long long)r.part_w_min, (long long)r.part_w_max, (long long)r.parts_over_bound,
+                (long long)r.empty_parts, (long long)r.cut_nets, (long long)r.connectivity, (long long)r.connectivity_w,
+                (long long)r.conn_w_before[r.levels], (long long)r.soed, iters, moves, o.kd_host ? "host" : "device",
+                r.t_total, r.t_match, r.t_contract, r.t_initial, r.t_jet, r.t_metrics, secs(t0),
+                base_name(o.input).c_str(), r.k, o.ml_wlap ? ", wlap=1" : "");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ek_cli_main(const char* tool_c, int argc, char** argv) {
@@ -662,7 +715,12 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.ml_eps = std::stod(need("--kway-multilevel"));
                 o.ml = o.kml = true;
                 if (!std::isfinite(o.ml_eps) || o.ml_eps < 0) throw Fail{"--kway-multilevel takes an imbalance >= 0"};
-            } else if (a == "--ml-coarse") {
+            } else if (a == "--kway-direct") {
+                o.kd = true;  // (before the value, as --refine-weighted)
+                o.kd_eps = std::stod(need("--kway-direct"));
+                if (!std::isfinite(o.kd_eps) || o.kd_eps < 0) throw Fail{"--kway-direct takes an imbalance >= 0"};
+            } else if (a == "--contract-host") o.kd_host = true;
+            else if (a == "--ml-coarse") {
                 o.ml_coarse = std::stoi(need("--ml-coarse"));
                 o.ml_sub = true;
                 if (o.ml_coarse < 1) throw Fail{"--ml-coarse takes a node count of at least 1"};
@@ -681,6 +739,7 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
                 a == "--jet-iters")
                 std::printf("%s", ML_USAGE);
+            if (a == "--kway-direct") std::printf("%s", KD_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
@@ -688,10 +747,23 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
                 a == "--jet-iters")
                 std::printf("%s", ML_USAGE);
+            if (a == "--kway-direct") std::printf("%s", KD_USAGE);
             return 1;
         }
     }
     try {
+        if (o.kd || o.kd_host) {  // the direct k-way path: refused with any other partitioner or refinement
+            if (!o.kd || o.kway < 2 || o.kway > 256 || o.ml || o.kml || o.refine || o.refine_w || o.jet || o.sweep ||
+                o.sweep_ratio || o.fm || o.fm_sub || o.weighted || o.sweep_weighted || o.no_kl || o.tool != "gKL2" ||
+                !(pos.size() == 2 && pos[1] == "-EIG")) {
+                std::printf("%s", KD_USAGE);
+                return 1;
+            }
+            mkdirs();
+            o.input = pos[0];
+            o.eig = true;
+            return run_kway_direct(o);
+        }
         if (o.refine_w && !o.kml) {  // --refine-weighted follows --kway-multilevel only
             std::printf("%s", ML_USAGE);
             return 1;

@@ -992,6 +992,34 @@ void match_round(hipStream_t s, const MatchDev& d, unsigned long long* slot);
 // cluster[] of mate[]; rank[n] = the clusters
 void match_cluster(hipStream_t s, const MatchDev& d);
 
+// kernels_contract.hip — the contraction (ek_hgr_contract_device, §19)
+constexpr int CONTRACT_THREADS = 256;  // a workgroup: 4 waves, a net a wave in the net kernels
+struct ContractDev {
+    int n, nc, nets, hash_bits;  // nodes, clusters, nets of the fine hypergraph; the grouping bits (1..64)
+    const int64_t* net_ptr;      // nets + 1, raw pins
+    const int32_t *pins, *cluster;
+    const int32_t *w, *cw;       // node and net weights; null: all ones
+    unsigned long long* wsum;    // nc, zero before: the clusters' weights
+    int* hits;                   // nc, zero before: the clusters' nodes
+    int32_t* node_w;             // nc: the coarse node weights
+    int32_t* dpins;              // raw pins: net e's distinct clusters, first occurrence first, from net_ptr[e]
+    int* dsz;                    // nets: how many
+    unsigned long long* key[2];  // nets: the grouping key (the signature's low hash_bits bits), and the sort's other buffer
+    int32_t* ids[2];             // nets: the net ids beside the keys
+    unsigned *table, *scan_tmp;  // the sort's: 256 * sweep_tiles(nets) words; sweep_scan_tmp_words of that
+    unsigned long long* csum;    // nets, zero before: the summed c of the class, at its least net
+    int *keep, *ksz;             // nets: 1 for a kept net; its distinct pins (0 for the others)
+    long long *idx, *off, *tiles;  // nets + 1: the exclusive scans of keep and ksz; their scratch, (nets + 1023) / 1024
+    int64_t* out_ptr;            // the coarse net_ptr (without its last entry)
+    int32_t *out_pins, *out_w;   // the coarse pins and net weights
+    int* err;                    // 3 words, zero before: unhit clusters, clusters and merged nets above 2^31 - 1
+};
+// wsum, hits, then node_w and err[0..1].  n > 0.
+void contract_nodes(hipStream_t s, const ContractDev& d);
+// everything else: dpins, the sort, the classes, the scans and the coarse nets;
+// idx[nets] = the coarse nets, off[nets] = the coarse pins, err[2].  nets > 0.
+void contract_nets(hipStream_t s, const ContractDev& d);
+
 }  // namespace dev
 }  // namespace ek
 

@@ -5,7 +5,8 @@
 // kernels_match.hip).  It is written from the rule (eigkl.h),
 // one plain loop per step of a round, not from the kernels.  The two share
 // only what is input: the argument checks and the participating nets with
-// their weights (match_check).  ek_hgr_contract has no device counterpart.
+// their weights (match_check).  ek_hgr_contract is what the device contraction
+// (ek_hgr_contract_device, ctx_contract.cpp) must equal byte for byte.
 #include <algorithm>
 #include <chrono>
 #include <memory>

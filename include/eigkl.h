@@ -1273,6 +1273,85 @@ int ek_kway_jet(ek_ctx* ctx, const ek_hgr* h, const ek_kway_jet_opts* opts, cons
                 int32_t* part_inout, int64_t* iter_log, int64_t log_iters, ek_kway_jet_result* result);
 
 /* ------------------------------------------------------------------ */
+/* Direct k-way multilevel: one coarsening, the Jet refinement at every  */
+/* level, contraction on the device.  No reference        */
+/* counterpart.                                                           */
+/* ------------------------------------------------------------------ */
+typedef struct {
+    int32_t hash_bits; /* the low bits of a net's 64-bit set signature that group the nets, 1..64; default 64 */
+    int32_t pad;
+} ek_contract_opts;
+void ek_contract_default_opts(ek_contract_opts* opts);
+/* ek_hgr_contract on the GPU: the same hypergraph byte for byte (nodes, nets,
+ * net_ptr, pins, node_w, net_w) and the same EK_EINVAL cases (an id outside
+ * [0, n_coarse), an unhit cluster, a cluster or merged-net weight above 2^31 -
+ * 1, a null argument), plus hash_bits outside 1..64.  Nets are grouped by the
+ * low hash_bits bits of an order-independent signature of their distinct pin
+ * set; inside a group two nets merge only after their sets compared equal pin
+ * by pin, so the result does not depend on hash_bits (a small value only makes
+ * the groups, and the call, larger).  Integer arithmetic and integer atomic adds
+ * only; the result does not depend on the order threads run in.  EK_ESTATE on a
+ * multi-rank context.  Keeps nothing on the context: every buffer is local to
+ * the call.  opts may be NULL. */
+int ek_hgr_contract_device(ek_ctx* ctx, const ek_hgr* h, const int32_t* cluster /* nodes */, int64_t n_coarse,
+                           const ek_contract_opts* opts, ek_hgr** out);
+
+#define EK_KWAY_DIRECT_HOST_CONTRACT 1     /* ek_hgr_contract in place of ek_hgr_contract_device */
+#define EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN 2 /* EK_ML_WEIGHTED_LAPLACIAN for the initial partition */
+typedef struct {
+    int32_t k;             /* number of parts, 2..256 */
+    int32_t flags;         /* EK_KWAY_DIRECT_*; any other bit: EK_EINVAL */
+    double imbalance;      /* epsilon >= 0; default 0.03: part_bound Lk = floor((1 + eps) ceil(W / k)) */
+    int32_t coarse_nodes;  /* coarsening stops at this many nodes; <= 0 (default): max(512, 128 k) */
+    int32_t max_levels;    /* default and maximum EK_ML_LEVELS; values outside [1, EK_ML_LEVELS] act as it */
+    ek_match_opts match;   /* max_cluster <= 0 (default): max(1, min(ceil(4 W / coarse_nodes), max(1, Lk - ceil(W / k)))) */
+    ek_kway_ml_opts initial; /* the coarsest level's partition: its ml is used; k, flags, imbalance, write_results
+                              * and out_dir are overwritten */
+    ek_kway_jet_opts jet;  /* every level's refinement: max_iters, patience, neg_num, neg_den are used; k and imbalance
+                            * are overwritten */
+    int32_t write_results; /* ek_partition_kway_direct_file: 1 writes results/<base>.part.<k> under out_dir */
+    int32_t pad;
+    const char* out_dir;   /* NULL: the CWD */
+} ek_kway_direct_opts;
+
+typedef struct {
+    int32_t k;
+    int32_t levels;            /* L: the coarse levels kept; level l of the arrays below is H_l, 0 <= l <= L */
+    int32_t initial_fallbacks; /* the initial partition's coarsest_fallbacks */
+    int32_t infeasible_sweeps; /* the initial partition's infeasible_sweeps */
+    int64_t nodes[EK_ML_LEVELS + 1], nets[EK_ML_LEVELS + 1], pins[EK_ML_LEVELS + 1];
+    int64_t match_rounds[EK_ML_LEVELS + 1], match_pairs[EK_ML_LEVELS + 1]; /* of the matching H_l -> H_(l+1), l < L */
+    int64_t conn_w_before[EK_ML_LEVELS + 1], conn_w_after[EK_ML_LEVELS + 1]; /* weighted connectivity around H_l's Jet */
+    int64_t jet_iters[EK_ML_LEVELS + 1], jet_moves[EK_ML_LEVELS + 1];
+    int64_t total_weight, part_bound, max_cluster; /* W; Lk; the matching's bound as used */
+    int64_t part_w_min, part_w_max, parts_over_bound, empty_parts;
+    int64_t cut_nets, connectivity, connectivity_w, soed; /* ek_kway_metrics_w of part_out on h */
+    double t_match, t_contract, t_initial, t_jet, t_metrics, t_total; /* wall seconds (host clock) */
+} ek_kway_direct_result;
+
+void ek_kway_direct_default_opts(ek_kway_direct_opts* opts);
+/* k-way partition of h by one multilevel cycle.  W = sum w(v), Lk = floor((1 +
+ * imbalance) ceil(W / k)).  (1) Coarsen as ek_multilevel_bipartition does:
+ * while H_l has more than coarse_nodes nodes and l < max_levels, ek_match; stop
+ * if 10 n_(l+1) > 9 n_l; otherwise contract (ek_hgr_contract_device, or
+ * ek_hgr_contract under EK_KWAY_DIRECT_HOST_CONTRACT: the same hypergraph).
+ * (2) ek_partition_kway_ml of the coarsest H_L with the same k and imbalance.
+ * (3) ek_kway_jet on H_L under the uniform bound, then for l = L - 1 .. 0:
+ * part_l[v] = part_(l+1)[cluster_l[v]] and ek_kway_jet on H_l.  (4) The final
+ * integers are ek_kway_metrics_w's on h.  conn_w_before[l] = conn_w_after[l +
+ * 1]; conn_w_after[l] <= conn_w_before[l]; projection keeps every part's
+ * weight; no part ends above max(Lk, its weight after the initial partition),
+ * and one above Lk is reported in parts_over_bound, not an error.  EK_ESTATE on
+ * a multi-rank context; EK_EINVAL for k outside 2..256, an imbalance that is
+ * negative or not finite, an unknown flag bit.  result may be NULL. */
+int ek_partition_kway_direct(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_opts* opts, int32_t* part_out /* nodes */,
+                             ek_kway_direct_result* result);
+/* The same on the hMETIS reading of a file (ek_hgr_read_weighted); part_out
+ * may be NULL.  With write_results: results/<base>.part.<k> under out_dir. */
+int ek_partition_kway_direct_file(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t* part_out,
+                                  ek_kway_direct_result* result);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
