@@ -200,6 +200,12 @@ class MatchResult(_AbiStruct):
                 ("eligible_nets", _I64), ("t_setup", ctypes.c_double), ("t_rounds", ctypes.c_double)]
 
 
+class ClusterResult(_AbiStruct):
+    """eigkl.h ek_cluster_result (the multi-node clustering of the coarsening)."""
+    _fields_ = [("n", _I64), ("n_coarse", _I64), ("joins", _I64), ("rounds", _I32), ("pad", _I32),
+                ("eligible_nets", _I64), ("heaviest", _I64), ("t_setup", ctypes.c_double), ("t_rounds", ctypes.c_double)]
+
+
 class MlOpts(_AbiStruct):
     _fields_ = [("imbalance", ctypes.c_double), ("coarse_nodes", _I32), ("max_levels", _I32), ("match", MatchOpts),
                 ("fm", FmOpts), ("lanczos", LanczosOpts)]
@@ -258,6 +264,9 @@ class ContractOpts(_AbiStruct):
 
 KWAY_DIRECT_HOST_CONTRACT = 1  # eigkl.h EK_KWAY_DIRECT_HOST_CONTRACT
 KWAY_DIRECT_WEIGHTED_LAPLACIAN = 2  # eigkl.h EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN
+COARSEN_MATCH = 0  # eigkl.h EK_COARSEN_MATCH
+COARSEN_CLUSTER = 1  # eigkl.h EK_COARSEN_CLUSTER
+_COARSENINGS = {"match": COARSEN_MATCH, "cluster": COARSEN_CLUSTER}
 
 
 class KwayDirectOpts(_AbiStruct):
@@ -422,6 +431,8 @@ _sig("ek_fm_refine_w", ctypes.c_int, _P, _P, ctypes.POINTER(FmOpts), _P, _P, _I6
 _sig("ek_match_default_opts", None, ctypes.POINTER(MatchOpts))
 _sig("ek_match_host", ctypes.c_int, _P, ctypes.POINTER(MatchOpts), _P, _P, _P, _I64, ctypes.POINTER(MatchResult))
 _sig("ek_match", ctypes.c_int, _P, _P, ctypes.POINTER(MatchOpts), _P, _P, _P, _I64, ctypes.POINTER(MatchResult))
+_sig("ek_cluster_host", ctypes.c_int, _P, ctypes.POINTER(MatchOpts), _P, _P, _P, _I64, ctypes.POINTER(ClusterResult))
+_sig("ek_cluster", ctypes.c_int, _P, _P, ctypes.POINTER(MatchOpts), _P, _P, _P, _I64, ctypes.POINTER(ClusterResult))
 _sig("ek_hgr_contract", ctypes.c_int, _P, _P, _I64, ctypes.POINTER(_P))
 _sig("ek_ml_default_opts", None, ctypes.POINTER(MlOpts))
 _sig("ek_multilevel_bipartition", ctypes.c_int, _P, _P, ctypes.POINTER(MlOpts), _P, ctypes.POINTER(MlResult))
@@ -453,6 +464,10 @@ _sig("ek_kway_direct_default_opts", None, ctypes.POINTER(KwayDirectOpts))
 _sig("ek_partition_kway_direct", ctypes.c_int, _P, _P, ctypes.POINTER(KwayDirectOpts), _P,
      ctypes.POINTER(KwayDirectResult))
 _sig("ek_partition_kway_direct_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayDirectOpts), _P,
+     ctypes.POINTER(KwayDirectResult))
+_sig("ek_partition_kway_direct_ex", ctypes.c_int, _P, _P, ctypes.POINTER(KwayDirectOpts), _I32, _P,
+     ctypes.POINTER(KwayDirectResult))
+_sig("ek_partition_kway_direct_file_ex", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayDirectOpts), _I32, _P,
      ctypes.POINTER(KwayDirectResult))
 
 lib = _lib
@@ -1043,6 +1058,40 @@ def match_host(hgr, max_cluster=2, max_net=64, max_rounds=8):
     return _match(lambda *a: _lib.ek_match_host(hgr._h, *a), "match_host", hgr, max_cluster, max_net, max_rounds)
 
 
+def _cluster(call, what, hgr, max_cluster, max_net, max_rounds):
+    """(rep, cluster, round log, result dict): the log has one row per round that joined, (proposers, movers, joins)."""
+    o = MatchOpts()
+    _lib.ek_match_default_opts(ctypes.byref(o))
+    o.max_net, o.max_rounds, o.max_cluster = int(max_net), int(max_rounds), int(max_cluster)
+    n = hgr.nodes
+    cap = int(max_rounds) if max_rounds > 0 else 64
+    while True:
+        rep = np.full(n, -2, np.int32)
+        cluster = np.full(n, -2, np.int32)
+        log = np.zeros((cap, 3), np.int64)
+        r = ClusterResult()
+        _chk(call(ctypes.byref(o), _p(rep), _p(cluster), _p(log), cap, ctypes.byref(r)), what)
+        if r.rounds <= cap:  # (else: deterministic, so the same run again with room for its log)
+            break
+        cap = r.rounds
+    res = {name: getattr(r, name) for name, _ in ClusterResult._fields_ if name != "pad"}
+    return rep, cluster, log[:r.rounds].copy(), res
+
+
+def cluster_host(hgr, max_cluster, max_net=64, max_rounds=8):
+    """The multi-node clustering of the coarsening on the host (ek_cluster_host, the checker of Context.cluster): a
+    single node joins the cluster of its best shared net of at most max_net pins while the cluster's weight stays at
+    most max_cluster.  Returns (rep, cluster, round log, result dict): rep[v] the root of v's cluster, cluster[v] the
+    rank of that root among the roots."""
+    return _cluster(lambda *a: _lib.ek_cluster_host(hgr._h, *a), "cluster_host", hgr, max_cluster, max_net, max_rounds)
+
+
+def _coarsening(name):
+    if name not in _COARSENINGS:
+        raise ValueError(f"coarsening {name!r}: one of {sorted(_COARSENINGS)}")
+    return _COARSENINGS[name]
+
+
 def _ml_opts(imbalance, coarse_nodes, max_levels, max_cluster, max_net, max_rounds, max_passes, stall, lanczos):
     o = MlOpts()
     _lib.ek_ml_default_opts(ctypes.byref(o))
@@ -1414,29 +1463,31 @@ class Context:
         return Hypergraph(c)
 
     def partition_kway_direct(self, hgr, k, eps=0.03, host_contract=False, weighted_laplacian=False, coarse_nodes=0,
-                              jet=None, initial=None):
-        """The direct k-way multilevel partition (ek_partition_kway_direct): one coarsening by matching and
+                              jet=None, initial=None, coarsening="match"):
+        """The direct k-way multilevel partition (ek_partition_kway_direct_ex): one coarsening by matching and
         contraction (on the device; host_contract: on the host, the same hypergraphs), partition_kway_ml of the
         coarsest level, then kway_jet at every level on the way back up, all under floor((1 + eps) ceil(W / k)).
-        coarse_nodes 0: max(512, 128 k).  jet / initial: option fields to override (see _kway_direct_opts).  Returns
-        (part id per node, result dict)."""
+        coarse_nodes 0: max(512, 128 k).  jet / initial: option fields to override (see _kway_direct_opts).
+        coarsening: "match" or "cluster" (Context.cluster in place of Context.match; match_rounds and match_pairs of
+        the result then hold its rounds and joins).  Returns (part id per node, result dict)."""
         o = _kway_direct_opts(k, eps, host_contract, weighted_laplacian, coarse_nodes, jet, initial, False, None)
         part = np.full(hgr.nodes, -1, np.int32)
         r = KwayDirectResult()
-        _chk(_lib.ek_partition_kway_direct(self._c, hgr._h, ctypes.byref(o), _p(part), ctypes.byref(r)),
-             "partition_kway_direct")
+        _chk(_lib.ek_partition_kway_direct_ex(self._c, hgr._h, ctypes.byref(o), _coarsening(coarsening), _p(part),
+                                              ctypes.byref(r)), "partition_kway_direct")
         return part, _kway_direct_result(r)
 
     def partition_kway_direct_file(self, path, k, eps=0.03, host_contract=False, weighted_laplacian=False,
-                                   coarse_nodes=0, jet=None, initial=None, write_results=True, out_dir=None):
+                                   coarse_nodes=0, jet=None, initial=None, write_results=True, out_dir=None,
+                                   coarsening="match"):
         """The same on the hMETIS reading of a file; write_results: results/<base>.part.<k> under out_dir
-        (ek_partition_kway_direct_file).  Returns (part id per node, result dict)."""
+        (ek_partition_kway_direct_file_ex).  Returns (part id per node, result dict)."""
         o = _kway_direct_opts(k, eps, host_contract, weighted_laplacian, coarse_nodes, jet, initial, write_results,
                               out_dir)
         part = np.full(Hypergraph.read_weighted(path).nodes, -1, np.int32)
         r = KwayDirectResult()
-        _chk(_lib.ek_partition_kway_direct_file(self._c, os.fsencode(path), ctypes.byref(o), _p(part), ctypes.byref(r)),
-             f"partition_kway_direct_file {path}")
+        _chk(_lib.ek_partition_kway_direct_file_ex(self._c, os.fsencode(path), ctypes.byref(o), _coarsening(coarsening),
+                                                   _p(part), ctypes.byref(r)), f"partition_kway_direct_file {path}")
         return part, _kway_direct_result(r)
 
     def partition_kway_ml_file(self, path, k, imbalance=0.03, coarse_nodes=512, weighted_laplacian=False,
@@ -1512,6 +1563,11 @@ class Context:
     def match(self, hgr, max_cluster=2, max_net=64, max_rounds=8):
         """match_host on the GPU (ek_match): the same mate, cluster, round log and result integers."""
         return _match(lambda *a: _lib.ek_match(self._c, hgr._h, *a), "match", hgr, max_cluster, max_net, max_rounds)
+
+    def cluster(self, hgr, max_cluster, max_net=64, max_rounds=8):
+        """cluster_host on the GPU (ek_cluster): the same rep, cluster, round log and result integers."""
+        return _cluster(lambda *a: _lib.ek_cluster(self._c, hgr._h, *a), "cluster", hgr, max_cluster, max_net,
+                        max_rounds)
 
     def multilevel_bipartition(self, hgr, imbalance=0.03, coarse_nodes=512, max_levels=ML_LEVELS, max_cluster=0,
                                max_net=64, max_rounds=8, max_passes=0, stall=1000, lanczos=None,

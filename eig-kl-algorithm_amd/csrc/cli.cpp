@@ -99,7 +99,9 @@
 //                        coarsening, the recursive driver on the coarsest level,
 //                        the Jet refinement at every level; --ml-coarse N,
 //                        --jet-iters I and --ml-weighted-laplacian apply;
-//                        --contract-host contracts on the host; excludes every
+//                        --contract-host contracts on the host; --coarsen
+//                        match|cluster chooses the coarsening (the matching by
+//                        default, DESIGN.md §20's clustering); excludes every
 //                        other partitioner and refinement flag; one line
 //                        beginning "kway-direct:", results/<base>.part.<N>
 //   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
@@ -174,7 +176,7 @@ int kway_ml_jet_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanc
 // kway_direct.cpp: ek_partition_kway_direct_file with the results file on, for `--k N --kway-direct EPS`
 // (coarse_nodes <= 0, max_iters <= 0: the defaults)
 int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
-                             int coarse_nodes, int max_iters, int32_t flags, ek_kway_direct_result* r)
+                             int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening, ek_kway_direct_result* r)
     __attribute__((weak));
 }
 
@@ -205,6 +207,8 @@ struct Opts {
     int jet_iters = 0;  // --jet-iters I (0: no limit)
     bool kd = false, kd_host = false;  // --kway-direct EPS (with --k); --contract-host (with --kway-direct)
     double kd_eps = 0.0;
+    bool kd_coarsen = false;  // --coarsen match|cluster seen (with --kway-direct)
+    int kd_cluster = 0;       // EK_COARSEN_MATCH | EK_COARSEN_CLUSTER
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -599,10 +603,11 @@ int run_kway_ml(const Opts& o) {
 
 constexpr const char* KD_USAGE =
     "Usage: gKL2 <input_file> -EIG --k <parts> --kway-direct <imbalance> [--ml-coarse <N>] [--jet-iters <I>] "
-    "[--contract-host] [--ml-weighted-laplacian]  (the direct k-way multilevel partition: one coarsening, the Jet "
-    "refinement at every level; needs --k with 2 <= parts <= 256 and an imbalance >= 0; excludes --kway-multilevel, "
-    "--multilevel, --refine, --refine-weighted, --refine-jet, --sweep and --fm; --contract-host contracts on the host; "
-    "the file is read as hMETIS reads it)\n";
+    "[--contract-host] [--ml-weighted-laplacian] [--coarsen match|cluster]  (the direct k-way multilevel partition: one "
+    "coarsening, the Jet refinement at every level; needs --k with 2 <= parts <= 256 and an imbalance >= 0; excludes "
+    "--kway-multilevel, --multilevel, --refine, --refine-weighted, --refine-jet, --sweep and --fm; --contract-host "
+    "contracts on the host; --coarsen cluster coarsens by multi-node clustering, match (the default) by matching; the file "
+    "is read as hMETIS reads it)\n";
 
 // gKL2 <in.hgr> -EIG --k N --kway-direct EPS: one summary line beginning "kway-direct:", results/<base>.part.<N>
 int run_kway_direct(const Opts& o) {
@@ -613,7 +618,7 @@ int run_kway_direct(const Opts& o) {
     ek_kway_direct_result r{};
     const int32_t flags = (o.kd_host ? EK_KWAY_DIRECT_HOST_CONTRACT : 0) | (o.ml_wlap ? EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN : 0);
     check(ek::kway_direct_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.kd_eps, o.ml_coarse, o.jet_iters,
-                                       flags, &r),
+                                       flags, o.kd_cluster, &r),
           "direct k-way partition");
     long long iters = 0, moves = 0;
     for (int l = 0; l <= r.levels; ++l) {
@@ -623,13 +628,13 @@ int run_kway_direct(const Opts& o) {
     std::printf("kway-direct: k %d, imbalance %g, levels %d, coarsest_nodes %lld, max_cluster %lld, fallbacks %d, "
                 "infeasible %d, total_weight %lld, part_bound %lld, part weights %lld..%lld, over_bound %lld, empty %lld, "
                 "cut nets %lld, connectivity %lld, connectivity_w %lld (initial %lld), SOED %lld, jet iterations %lld, "
-                "jet moves %lld, contract %s, %.3f s (match %.3f, contract %.3f, initial %.3f, jet %.3f, metrics %.3f), "
+                "jet moves %lld, contract %s, coarsen %s, %.3f s (match %.3f, contract %.3f, initial %.3f, jet %.3f, metrics %.3f), "
                 "%.3f s -> results/%s.part.%d%s\n", r.k, o.kd_eps, r.levels, (long long)r.nodes[r.levels],
                 (long long)r.max_cluster, r.initial_fallbacks, r.infeasible_sweeps, (long long)r.total_weight,
                 (long long)r.part_bound, (long long)r.part_w_min, (long long)r.part_w_max, (long long)r.parts_over_bound,
                 (long long)r.empty_parts, (long long)r.cut_nets, (long long)r.connectivity, (long long)r.connectivity_w,
                 (long long)r.conn_w_before[r.levels], (long long)r.soed, iters, moves, o.kd_host ? "host" : "device",
-                r.t_total, r.t_match, r.t_contract, r.t_initial, r.t_jet, r.t_metrics, secs(t0),
+                o.kd_cluster == EK_COARSEN_CLUSTER ? "cluster" : "match", r.t_total, r.t_match, r.t_contract, r.t_initial, r.t_jet, r.t_metrics, secs(t0),
                 base_name(o.input).c_str(), r.k, o.ml_wlap ? ", wlap=1" : "");
     return 0;
 }
@@ -720,6 +725,13 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.kd_eps = std::stod(need("--kway-direct"));
                 if (!std::isfinite(o.kd_eps) || o.kd_eps < 0) throw Fail{"--kway-direct takes an imbalance >= 0"};
             } else if (a == "--contract-host") o.kd_host = true;
+            else if (a == "--coarsen") {
+                o.kd_coarsen = true;  // (before the value, as --refine-weighted)
+                const std::string v = need("--coarsen");
+                if (v == "match") o.kd_cluster = EK_COARSEN_MATCH;
+                else if (v == "cluster") o.kd_cluster = EK_COARSEN_CLUSTER;
+                else throw Fail{"--coarsen takes match or cluster"};
+            }
             else if (a == "--ml-coarse") {
                 o.ml_coarse = std::stoi(need("--ml-coarse"));
                 o.ml_sub = true;
@@ -739,7 +751,7 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
                 a == "--jet-iters")
                 std::printf("%s", ML_USAGE);
-            if (a == "--kway-direct") std::printf("%s", KD_USAGE);
+            if (a == "--kway-direct" || a == "--coarsen") std::printf("%s", KD_USAGE);
             return 1;
         } catch (...) {
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
@@ -747,12 +759,12 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
                 a == "--jet-iters")
                 std::printf("%s", ML_USAGE);
-            if (a == "--kway-direct") std::printf("%s", KD_USAGE);
+            if (a == "--kway-direct" || a == "--coarsen") std::printf("%s", KD_USAGE);
             return 1;
         }
     }
     try {
-        if (o.kd || o.kd_host) {  // the direct k-way path: refused with any other partitioner or refinement
+        if (o.kd || o.kd_host || o.kd_coarsen) {  // the direct k-way path: refused with any other partitioner or refinement
             if (!o.kd || o.kway < 2 || o.kway > 256 || o.ml || o.kml || o.refine || o.refine_w || o.jet || o.sweep ||
                 o.sweep_ratio || o.fm || o.fm_sub || o.weighted || o.sweep_weighted || o.no_kl || o.tool != "gKL2" ||
                 !(pos.size() == 2 && pos[1] == "-EIG")) {

@@ -992,6 +992,36 @@ void match_round(hipStream_t s, const MatchDev& d, unsigned long long* slot);
 // cluster[] of mate[]; rank[n] = the clusters
 void match_cluster(hipStream_t s, const MatchDev& d);
 
+// kernels_cluster.hip — the multi-node clustering (ek_cluster, §20).  score[]
+// and entries[] are the matching's (match_prepare).
+constexpr int CLUSTER_THREADS = 256;  // a workgroup of the node kernels
+constexpr int CLUSTER_SHORT = 32;     // up to this many movers a destination's segment is its thread's, above it its wave's
+struct ClusterDev {
+    int n;
+    long long cap;                     // max_cluster
+    const int64_t *net_ptr, *inc_ptr;  // nets + 1: distinct pins; n + 1: the nodes' nets
+    const int32_t *pins, *inc, *w;
+    const long long* score;    // per net: score(e), -1 when the net is not eligible
+    const int32_t* entries;    // per node: its pins' count over its eligible nets, itself excluded
+    int32_t* rep;              // n: the root of the node's cluster
+    long long* S;              // n: the cluster weight, at the root
+    int* grown;                // n: 1 once the node has joined or been joined (no longer single)
+    int32_t* t;                // n: the round's proposal, -1 for none
+    long long* sigma;          // n: its score
+    int *in, *mover, *acc;     // n: proposed to; moves this round; accepted this round
+    int *count, *cursor;       // n: the movers of a destination; its scatter cursor
+    long long *off, *tiles;    // n + 1: the exclusive scan of count (and of the root flags); its scratch, (n + 1023) / 1024
+    int32_t* seg;              // n: the movers, grouped by destination from off[]
+    int32_t* cluster;
+};
+// rep[] = v, S[] = w, grown[] = 0
+void cluster_init(hipStream_t s, const ClusterDev& d);
+// one round, all of it from the state at its start.  slot (device, zero
+// before): the round's proposers, movers and joins
+void cluster_round(hipStream_t s, const ClusterDev& d, unsigned long long* slot);
+// cluster[] of rep[]; off[n] = the clusters (count[] is overwritten by the root flags)
+void cluster_number(hipStream_t s, const ClusterDev& d);
+
 // kernels_contract.hip — the contraction (ek_hgr_contract_device, §19)
 constexpr int CONTRACT_THREADS = 256;  // a workgroup: 4 waves, a net a wave in the net kernels
 struct ContractDev {

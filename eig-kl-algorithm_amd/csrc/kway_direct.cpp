@@ -29,7 +29,7 @@ void chk(int rc) {
 
 using Hgr = std::unique_ptr<ek_hgr, void (*)(ek_hgr*)>;
 
-void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, int32_t* part_out,
+void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, int32_t coarsening, int32_t* part_out,
                ek_kway_direct_result* result) {
     const auto t0 = clk::now();
     ek_kway_direct_opts o;
@@ -45,6 +45,8 @@ void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, in
     if (o.flags & ~int32_t(EK_KWAY_DIRECT_HOST_CONTRACT | EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN))
         ek::fail(EK_EINVAL, "ek_partition_kway_direct: unknown flag bits 0x%x", unsigned(o.flags));
     if (h.nodes > INT32_MAX - 1) ek::fail(EK_EINVAL, "ek_partition_kway_direct: %lld nodes", (long long)h.nodes);
+    if (coarsening != EK_COARSEN_MATCH && coarsening != EK_COARSEN_CLUSTER)
+        ek::fail(EK_EINVAL, "ek_partition_kway_direct: coarsening %d (EK_COARSEN_MATCH or EK_COARSEN_CLUSTER)", int(coarsening));
     if (o.coarse_nodes <= 0) o.coarse_nodes = std::max(512, 128 * o.k);
     if (o.max_levels < 1 || o.max_levels > EK_ML_LEVELS) o.max_levels = EK_ML_LEVELS;
     ek_kway_direct_result r{};
@@ -70,7 +72,15 @@ void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, in
         auto t = clk::now();
         std::vector<int32_t> cl(static_cast<size_t>(cur->nodes));
         ek_match_result mr{};
-        chk(ek_match(ctx, cur, &o.match, nullptr, cl.data(), nullptr, 0, &mr));
+        if (coarsening == EK_COARSEN_CLUSTER) {  // §20: the same seam, the clustering's rounds and joins
+            ek_cluster_result cr{};
+            chk(ek_cluster(ctx, cur, &o.match, nullptr, cl.data(), nullptr, 0, &cr));
+            mr.n_coarse = cr.n_coarse;
+            mr.rounds = cr.rounds;
+            mr.pairs = cr.joins;
+        } else {
+            chk(ek_match(ctx, cur, &o.match, nullptr, cl.data(), nullptr, 0, &mr));
+        }
         r.t_match += since(t);
         if (10 * mr.n_coarse > 9 * cur->nodes) break;  // less than 10 % fewer nodes: not worth a level
         t = clk::now();
@@ -151,11 +161,12 @@ void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, in
 
 namespace ek {
 // `gKL2 <in> -EIG --k N --kway-direct EPS [--ml-coarse N] [--jet-iters I] [--contract-host]
-// [--ml-weighted-laplacian]` (cli.cpp refers to it weakly); coarse_nodes <= 0, max_iters <= 0: the defaults
+// [--ml-weighted-laplacian] [--coarsen match|cluster]` (cli.cpp refers to it weakly); coarse_nodes <= 0, max_iters <= 0:
+// the defaults
 int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
-                             int coarse_nodes, int max_iters, int32_t flags, ek_kway_direct_result* r);
+                             int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening, ek_kway_direct_result* r);
 int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
-                             int coarse_nodes, int max_iters, int32_t flags, ek_kway_direct_result* r) {
+                             int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening, ek_kway_direct_result* r) {
     ek_kway_direct_opts o;
     ek_kway_direct_default_opts(&o);
     o.k = k;
@@ -165,7 +176,7 @@ int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanc
     if (coarse_nodes > 0) o.coarse_nodes = coarse_nodes;
     if (max_iters > 0) o.jet.max_iters = max_iters;
     if (lanczos) o.initial.ml.lanczos = *lanczos;
-    return ek_partition_kway_direct_file(ctx, path, &o, nullptr, r);
+    return ek_partition_kway_direct_file_ex(ctx, path, &o, coarsening, nullptr, r);
 }
 }  // namespace ek
 
@@ -186,17 +197,29 @@ void ek_kway_direct_default_opts(ek_kway_direct_opts* o) {
 
 int ek_partition_kway_direct(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_opts* opts, int32_t* part_out,
                              ek_kway_direct_result* result) {
+    return ek_partition_kway_direct_ex(ctx, h, opts, EK_COARSEN_MATCH, part_out, result);
+}
+
+int ek_partition_kway_direct_ex(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                int32_t* part_out, ek_kway_direct_result* result) {
     EK_TRY
     if (!ctx || !h || (h->nodes > 0 && !part_out)) ek::fail(EK_EINVAL, "ek_partition_kway_direct: null argument");
-    partition(ctx, *h, opts, part_out, result);
+    partition(ctx, *h, opts, coarsening, part_out, result);
     return EK_OK;
     EK_CATCH
 }
 
 int ek_partition_kway_direct_file(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t* part_out,
                                   ek_kway_direct_result* result) {
+    return ek_partition_kway_direct_file_ex(ctx, path, opts, EK_COARSEN_MATCH, part_out, result);
+}
+
+int ek_partition_kway_direct_file_ex(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                     int32_t* part_out, ek_kway_direct_result* result) {
     EK_TRY
     if (!ctx || !path) ek::fail(EK_EINVAL, "ek_partition_kway_direct_file: null argument");
+    if (coarsening != EK_COARSEN_MATCH && coarsening != EK_COARSEN_CLUSTER)  // before the file is read
+        ek::fail(EK_EINVAL, "ek_partition_kway_direct_file: coarsening %d (EK_COARSEN_MATCH or EK_COARSEN_CLUSTER)", int(coarsening));
     ek_hgr* h = nullptr;
     chk(ek_hgr_read_weighted(path, &h));
     Hgr hg(h, ek_hgr_free);
@@ -206,7 +229,7 @@ int ek_partition_kway_direct_file(ek_ctx* ctx, const char* path, const ek_kway_d
         part_out = own.data();
     }
     ek_kway_direct_result r{};
-    partition(ctx, *h, opts, part_out, &r);
+    partition(ctx, *h, opts, coarsening, part_out, &r);
     if (opts && opts->write_results) ek::write_part_file(path, opts->out_dir, r.k, h->nodes, part_out);
     if (result) *result = r;
     return EK_OK;

@@ -933,6 +933,58 @@ int ek_match_host(const ek_hgr* h, const ek_match_opts* opts, int32_t* mate_out,
  * the context keeps nothing. */
 int ek_match(ek_ctx* ctx, const ek_hgr* h, const ek_match_opts* opts, int32_t* mate_out, int32_t* cluster_out,
              int64_t* round_log, int64_t log_rounds, ek_match_result* result);
+
+/* The clustering rule: a coarsening in which a node may join a
+ * cluster of more than two nodes.  All integers, every tie broken by ids.  The
+ * input, the options (ek_match_opts: max_cluster >= 1 bounds a cluster's
+ * weight), eligibility and score(e) are the matching's.
+ * State: rep[v], initially v; S(r), the weight of the cluster whose root is r
+ * (int64, initially w(r)).  A node u is single iff rep[u] = u and nothing has
+ * joined it.  A root never moves once something has joined it; a node that
+ * has joined never moves again.
+ * One round, every step reading the state at the round's start:
+ * (1) Propose.  Every single u looks at the entries (e, v) with e eligible, u
+ *     and v pins of e, v != u, r = rep[v] and S(r) + w(u) <= max_cluster; t(u)
+ *     is the r of the entry of greatest (score(e), then smaller r), sigma(u)
+ *     that score; -1 without an entry and for a node that is not single.
+ * (2) Incoming.  in[v] = 1 iff some u has t(u) = v.
+ * (3) Resolve.  ml(x): t(x) = z >= 0, t(z) = x and x > z (the larger id of a
+ *     mutual pair of singles).  u is a mover iff t(u) = r >= 0, (in[u] = 0 or
+ *     ml(u)) and not ml(r): a single that others propose to stays put unless
+ *     it is the larger of a mutual pair, and a node whose target is itself
+ *     leaving waits a round.
+ * (4) Accept.  Per destination r the movers with t = r are ordered by (sigma
+ *     descending, id ascending); a mover is accepted iff the sum of w over
+ *     the order up to and including it is at most max_cluster - S(r).
+ * (5) Apply.  Accepted u: rep[u] = r, S(r) += w(u); u and r are single no more.
+ * The run ends with the first round that accepts nothing (not counted, not
+ * logged) or after max_rounds rounds.  A round with a proposer accepts at
+ * least one node, so max_rounds <= 0 ends where no single node fits into a
+ * cluster it shares an eligible net with.  Every cluster of more than one node
+ * weighs at most max_cluster.  cluster[v] = the rank of rep[v] among the roots
+ * (rep[x] = x) in ascending id order; n_coarse = the number of roots. */
+typedef struct {
+    int64_t n, n_coarse, joins; /* nodes; clusters; accepted moves = n - n_coarse */
+    int32_t rounds, pad;        /* rounds that accepted at least one node */
+    int64_t eligible_nets;
+    int64_t heaviest;           /* the greatest S(r) over the roots (a single node may outweigh max_cluster) */
+    double t_setup, t_rounds;   /* wall seconds (host clock) */
+} ek_cluster_result;
+
+/* The clustering on the host (no GPU): the checker of ek_cluster, single
+ * threaded and written from the rule.  rep_out and cluster_out: one value per
+ * node of h, either may be NULL.  round_log (may be NULL) receives three values
+ * per round, for the first log_rounds rounds: proposers (t(u) >= 0), movers and
+ * joins.  opts NULL: ek_match_default_opts.  EK_EINVAL as ek_match_host. */
+int ek_cluster_host(const ek_hgr* h, const ek_match_opts* opts, int32_t* rep_out, int32_t* cluster_out,
+                    int64_t* round_log, int64_t log_rounds, ek_cluster_result* result);
+/* The same on the GPU: the same rep, cluster, round log and result integers,
+ * whatever order the workgroups run in.  The host reads one 8-byte counter per
+ * round.  EK_ESTATE on a multi-rank context.  Every buffer is local to the call
+ * and the context keeps nothing. */
+int ek_cluster(ek_ctx* ctx, const ek_hgr* h, const ek_match_opts* opts, int32_t* rep_out, int32_t* cluster_out,
+               int64_t* round_log, int64_t log_rounds, ek_cluster_result* result);
+
 /* The contraction of h along cluster (host only): any map of h's nodes onto
  * [0, n_coarse) that hits every value.  A coarse node weighs the sum of its
  * nodes' w(v).  Every net of h, in file order, is mapped through cluster, its
@@ -1350,6 +1402,18 @@ int ek_partition_kway_direct(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_
  * may be NULL.  With write_results: results/<base>.part.<k> under out_dir. */
 int ek_partition_kway_direct_file(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t* part_out,
                                   ek_kway_direct_result* result);
+/* The same with the coarsening of step (1) chosen.  EK_COARSEN_MATCH is
+ * ek_partition_kway_direct itself, byte for byte.  EK_COARSEN_CLUSTER calls
+ * ek_cluster where the loop calls ek_match, under the same
+ * opts.match, the same max_cluster default, the same 10 % rule and the same
+ * contraction; match_rounds and match_pairs of the result then hold the
+ * clustering's rounds and joins.  Any other value: EK_EINVAL. */
+#define EK_COARSEN_MATCH 0
+#define EK_COARSEN_CLUSTER 1
+int ek_partition_kway_direct_ex(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                int32_t* part_out /* nodes */, ek_kway_direct_result* result);
+int ek_partition_kway_direct_file_ex(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                     int32_t* part_out, ek_kway_direct_result* result);
 
 /* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
