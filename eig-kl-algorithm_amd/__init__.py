@@ -139,6 +139,19 @@ class KwayJetResult(_AbiStruct):
                 + [(k, ctypes.c_double) for k in ("t_setup", "t_iters", "t_metrics")])
 
 
+class KwayRebalanceOpts(_AbiStruct):
+    _fields_ = [("k", _I32), ("max_rounds", _I32), ("imbalance", ctypes.c_double)]
+
+
+class KwayRebalanceResult(_AbiStruct):
+    _fields_ = ([("k", _I32), ("rounds", _I32)]
+                + [(k, _I64) for k in ("moves", "total_weight", "bound_min", "bound_max", "parts_over_before",
+                                       "parts_over_bound", "excess_before", "excess", "connectivity_w_before",
+                                       "connectivity_w", "cut_nets", "connectivity", "soed", "part_w_min",
+                                       "part_w_max")]
+                + [(k, ctypes.c_double) for k in ("t_setup", "t_rounds", "t_metrics")])
+
+
 class SweepOpts(_AbiStruct):
     _fields_ = [("objective", _I32), ("pad", _I32), ("imbalance", ctypes.c_double)]
 
@@ -290,6 +303,15 @@ class KwayDirectResult(_AbiStruct):
                 + [(k, _I64) for k in _KWAY_DIRECT_INTS] + [(k, ctypes.c_double) for k in _KWAY_DIRECT_TIMES])
 
 
+_KWAY_DIRECT_RB_LEVEL_FIELDS = ("over_before", "excess_before", "rb_rounds", "rb_moves", "excess_after")
+
+
+class KwayDirectRbResult(_AbiStruct):
+    """eigkl.h ek_kway_direct_rb_result."""
+    _fields_ = ([(k, _I64 * (ML_LEVELS + 1)) for k in _KWAY_DIRECT_RB_LEVEL_FIELDS]
+                + [("t_rebalance", ctypes.c_double)])
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64,
                                 ctypes.POINTER(ctypes.c_double))
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _I64)
@@ -407,6 +429,11 @@ _sig("ek_kway_jet_host", ctypes.c_int, _P, ctypes.POINTER(KwayJetOpts), _P, _P, 
      ctypes.POINTER(KwayJetResult))
 _sig("ek_kway_jet", ctypes.c_int, _P, _P, ctypes.POINTER(KwayJetOpts), _P, _P, _P, _I64,
      ctypes.POINTER(KwayJetResult))
+_sig("ek_kway_rebalance_default_opts", None, ctypes.POINTER(KwayRebalanceOpts))
+_sig("ek_kway_rebalance_host", ctypes.c_int, _P, ctypes.POINTER(KwayRebalanceOpts), _P, _P, _P, _I64,
+     ctypes.POINTER(KwayRebalanceResult))
+_sig("ek_kway_rebalance", ctypes.c_int, _P, _P, ctypes.POINTER(KwayRebalanceOpts), _P, _P, _P, _I64,
+     ctypes.POINTER(KwayRebalanceResult))
 _sig("ek_sweep_default_opts", None, ctypes.POINTER(SweepOpts))
 _sig("ek_sweep_cut_host", ctypes.c_int, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
 _sig("ek_sweep_cut", ctypes.c_int, _P, _P, _P, ctypes.POINTER(SweepOpts), _P, _P, ctypes.POINTER(SweepResult))
@@ -469,6 +496,10 @@ _sig("ek_partition_kway_direct_ex", ctypes.c_int, _P, _P, ctypes.POINTER(KwayDir
      ctypes.POINTER(KwayDirectResult))
 _sig("ek_partition_kway_direct_file_ex", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayDirectOpts), _I32, _P,
      ctypes.POINTER(KwayDirectResult))
+_sig("ek_partition_kway_direct_rb", ctypes.c_int, _P, _P, ctypes.POINTER(KwayDirectOpts), _I32, _P,
+     ctypes.POINTER(KwayDirectResult), ctypes.POINTER(KwayDirectRbResult))
+_sig("ek_partition_kway_direct_rb_file", ctypes.c_int, _P, ctypes.c_char_p, ctypes.POINTER(KwayDirectOpts), _I32, _P,
+     ctypes.POINTER(KwayDirectResult), ctypes.POINTER(KwayDirectRbResult))
 
 lib = _lib
 
@@ -824,6 +855,40 @@ def kway_jet_host(hgr, part, k, eps=0.03, bounds=None, max_iters=0, patience=12,
     the best state seen."""
     return _kway_jet(lambda *a: _lib.ek_kway_jet_host(hgr._h, *a), "kway_jet_host", hgr, part, k, eps, bounds,
                      max_iters, patience, neg)
+
+
+def _kway_rebalance(call, what, hgr, part, k, imbalance, bounds, max_rounds):
+    """_kway_refine_w for the rebalancing entries."""
+    start = np.ascontiguousarray(part, np.int32)
+    if len(start) != hgr.nodes:
+        raise ValueError(f"part has {len(start)} entries for {hgr.nodes} nodes")
+    if bounds is not None:
+        bounds = np.ascontiguousarray(bounds, np.int64)
+        if len(bounds) != int(k):
+            raise ValueError(f"{len(bounds)} bounds for {k} parts")
+    o = KwayRebalanceOpts()
+    _lib.ek_kway_rebalance_default_opts(ctypes.byref(o))
+    o.k, o.max_rounds, o.imbalance = int(k), int(max_rounds), float(imbalance)
+    cap = int(max_rounds) if max_rounds > 0 else 256
+    while True:
+        out = start.copy()
+        log = np.zeros((cap, 4), np.int64)
+        r = KwayRebalanceResult()
+        _chk(call(ctypes.byref(o), _p(bounds), _p(out), _p(log), cap, ctypes.byref(r)), what)
+        if r.rounds <= cap:  # (else: deterministic, so the same run again with room for its log)
+            break
+        cap = r.rounds
+    res = {name: getattr(r, name) for name, _ in KwayRebalanceResult._fields_}
+    return out, res, log[:r.rounds].copy()
+
+
+def kway_rebalance_host(hgr, part, k, eps=0.03, bounds=None, max_rounds=0):
+    """k-way rebalancing on the host (ek_kway_rebalance_host, the device path's checker): the nodes of the parts above
+    bounds[p] (or above floor((1 + eps) ceil(W / k)) when bounds is None) move to parts with room until no part is
+    above its bound or nothing fits.  Returns (part, result dict, round log); a log row is (proposers, evicted nodes,
+    moved nodes, the excess after the round).  The weighted connectivity may rise."""
+    return _kway_rebalance(lambda *a: _lib.ek_kway_rebalance_host(hgr._h, *a), "kway_rebalance_host", hgr, part, k,
+                           eps, bounds, max_rounds)
 
 
 def _sweep_opts(imbalance, ratio):
@@ -1463,16 +1528,28 @@ class Context:
         return Hypergraph(c)
 
     def partition_kway_direct(self, hgr, k, eps=0.03, host_contract=False, weighted_laplacian=False, coarse_nodes=0,
-                              jet=None, initial=None, coarsening="match"):
+                              jet=None, initial=None, coarsening="match", rebalance=False):
         """The direct k-way multilevel partition (ek_partition_kway_direct_ex): one coarsening by matching and
         contraction (on the device; host_contract: on the host, the same hypergraphs), partition_kway_ml of the
         coarsest level, then kway_jet at every level on the way back up, all under floor((1 + eps) ceil(W / k)).
         coarse_nodes 0: max(512, 128 k).  jet / initial: option fields to override (see _kway_direct_opts).
         coarsening: "match" or "cluster" (Context.cluster in place of Context.match; match_rounds and match_pairs of
-        the result then hold its rounds and joins).  Returns (part id per node, result dict)."""
+        the result then hold its rounds and joins).  rebalance: ek_partition_kway_direct_rb, kway_rebalance before the
+        Jet refinement of every level that starts above the bound; the result dict then also holds, per level,
+        over_before, excess_before, rb_rounds, rb_moves and excess_after, and t_rebalance.
+        Returns (part id per node, result dict)."""
         o = _kway_direct_opts(k, eps, host_contract, weighted_laplacian, coarse_nodes, jet, initial, False, None)
         part = np.full(hgr.nodes, -1, np.int32)
         r = KwayDirectResult()
+        if rebalance:
+            rb = KwayDirectRbResult()
+            _chk(_lib.ek_partition_kway_direct_rb(self._c, hgr._h, ctypes.byref(o), _coarsening(coarsening), _p(part),
+                                                  ctypes.byref(r), ctypes.byref(rb)), "partition_kway_direct")
+            out = _kway_direct_result(r)
+            for name in _KWAY_DIRECT_RB_LEVEL_FIELDS:
+                out[name] = list(getattr(rb, name))[:r.levels + 1]
+            out["t_rebalance"] = rb.t_rebalance
+            return part, out
         _chk(_lib.ek_partition_kway_direct_ex(self._c, hgr._h, ctypes.byref(o), _coarsening(coarsening), _p(part),
                                               ctypes.byref(r)), "partition_kway_direct")
         return part, _kway_direct_result(r)
@@ -1559,6 +1636,12 @@ class Context:
         log.  Returns (part, result dict, iteration log)."""
         return _kway_jet(lambda *a: _lib.ek_kway_jet(self._c, hgr._h, *a), "kway_jet", hgr, part, k, eps, bounds,
                          max_iters, patience, neg)
+
+    def kway_rebalance(self, hgr, part, k, eps=0.03, bounds=None, max_rounds=0):
+        """kway_rebalance_host on the GPU (ek_kway_rebalance): the same part vector, result integers and round
+        log."""
+        return _kway_rebalance(lambda *a: _lib.ek_kway_rebalance(self._c, hgr._h, *a), "kway_rebalance", hgr, part, k,
+                               eps, bounds, max_rounds)
 
     def match(self, hgr, max_cluster=2, max_net=64, max_rounds=8):
         """match_host on the GPU (ek_match): the same mate, cluster, round log and result integers."""

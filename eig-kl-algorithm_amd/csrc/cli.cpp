@@ -104,6 +104,14 @@
 //                        default, DESIGN.md §20's clustering); excludes every
 //                        other partitioner and refinement flag; one line
 //                        beginning "kway-direct:", results/<base>.part.<N>
+//   --rebalance          with --kway-direct: ek_partition_kway_direct_rb_file, the
+//                        rebalancing (ek_kway_rebalance) before the
+//                        Jet refinement of every level that starts above the
+//                        bound; one more line beginning "rebalance:"
+//   --rebalance-to EPS2  with --kway-multilevel: then ek_kway_rebalance under
+//                        floor((1 + EPS2) ceil(W / N)), before --refine-jet if
+//                        given; excludes --refine-weighted; one more line
+//                        beginning "rebalance:"
 //   --ml-weighted-laplacian  with --multilevel: the coarsest level's Laplacian
 //                        carries its net weights (EK_ML_WEIGHTED_LAPLACIAN,
 //                        -(2 c(e) / |e|) per pin pair); the "ml:" line ends
@@ -178,6 +186,17 @@ int kway_ml_jet_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanc
 int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
                              int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening, ek_kway_direct_result* r)
     __attribute__((weak));
+// kway_direct.cpp: the same through ek_partition_kway_direct_rb_file, for `--k N --kway-direct EPS --rebalance`
+int kway_direct_rb_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                                int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening,
+                                ek_kway_direct_result* r, ek_kway_direct_rb_result* rb) __attribute__((weak));
+// kway_rebalance.cpp: ek_partition_kway_ml on the hMETIS reading of the file, then ek_kway_rebalance at
+// rb_imbalance, then (jet_imbalance >= 0) ek_kway_jet, then the results file, for `--k N --kway-multilevel EPS
+// --rebalance-to EPS2 [--refine-jet EPS3]`
+int kway_ml_rebalance_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                                   int coarse_nodes, int max_passes, int stall, int32_t flags, double rb_imbalance,
+                                   double jet_imbalance, int max_iters, ek_kway_ml_result* mr,
+                                   ek_kway_rebalance_result* rr, ek_kway_jet_result* jr) __attribute__((weak));
 }
 
 namespace {
@@ -209,6 +228,9 @@ struct Opts {
     double kd_eps = 0.0;
     bool kd_coarsen = false;  // --coarsen match|cluster seen (with --kway-direct)
     int kd_cluster = 0;       // EK_COARSEN_MATCH | EK_COARSEN_CLUSTER
+    bool rb = false;          // --rebalance (with --kway-direct)
+    bool rbt = false;         // --rebalance-to EPS2 (with --kway-multilevel)
+    double rbt_eps = 0.0;
     double ml_eps = 0.0;
     int ml_coarse = 0;  // --ml-coarse N (0: the default)
     bool spectra = false;
@@ -525,6 +547,9 @@ constexpr const char* ML_USAGE =
     "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> --refine-jet <imbalance> "
     "[--jet-iters <I>]  (then the Jet refinement under floor((1 + imbalance) ceil(W / parts)); needs "
     "--kway-multilevel, excludes --refine-weighted; the refine-jet: line follows)\n"
+    "Usage: gKL2 <input_file> -EIG --k <parts> --kway-multilevel <imbalance> --rebalance-to <imbalance> "
+    "[--refine-jet <imbalance>]  (then the rebalancing under floor((1 + imbalance) ceil(W / parts)), before the Jet "
+    "refinement if any; needs --kway-multilevel, excludes --refine-weighted; the rebalance: line follows)\n"
     "Usage: gKL2 <input_file> -EIG --multilevel <imbalance> --ml-weighted-laplacian  (the coarsest level's Laplacian "
     "carries its net weights, -(2 c(e) / |e|) per pin pair; needs --multilevel; the ml: line ends with wlap=1)\n";
 
@@ -558,7 +583,14 @@ int run_kway_ml(const Opts& o) {
     ek_kway_ml_result r{};
     ek_kway_refine_w_result rr{};
     ek_kway_jet_result jr{};
-    if (o.jet) {
+    ek_kway_rebalance_result br{};
+    if (o.rbt) {
+        if (!ek::kway_ml_rebalance_file_for_cli) throw Fail{"this build carries no k-way rebalancing"};
+        check(ek::kway_ml_rebalance_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse,
+                                                 o.fm_passes, o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0,
+                                                 o.rbt_eps, o.jet ? o.jet_eps : -1.0, o.jet_iters, &r, &br, &jr),
+              "multilevel k-way partition and rebalancing");
+    } else if (o.jet) {
         if (!ek::kway_ml_jet_file_for_cli) throw Fail{"this build carries no Jet refinement"};
         check(ek::kway_ml_jet_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.ml_eps, o.ml_coarse,
                                            o.fm_passes, o.fm_stall, o.ml_wlap ? EK_ML_WEIGHTED_LAPLACIAN : 0, o.jet_eps,
@@ -591,6 +623,13 @@ int run_kway_ml(const Opts& o) {
                     rr.rounds, (long long)rr.moves, (long long)rr.connectivity_w_before, (long long)rr.connectivity_w,
                     (long long)rr.cut_nets, (long long)rr.part_w_min, (long long)rr.part_w_max,
                     (long long)rr.parts_over_bound, rr.t_setup + rr.t_rounds + rr.t_metrics);
+    if (o.rbt)
+        std::printf("rebalance: imbalance %g (bound %lld), levels rebalanced %d, %d rounds, %lld moves, excess %lld -> "
+                    "%lld, over_bound %lld -> %lld, connectivity_w %lld -> %lld, %.3f s\n", o.rbt_eps,
+                    (long long)br.bound_max, br.parts_over_before > 0 ? 1 : 0, br.rounds, (long long)br.moves,
+                    (long long)br.excess_before, (long long)br.excess, (long long)br.parts_over_before,
+                    (long long)br.parts_over_bound, (long long)br.connectivity_w_before, (long long)br.connectivity_w,
+                    br.t_setup + br.t_rounds + br.t_metrics);
     if (o.jet)
         std::printf("refine-jet: imbalance %g (bound %lld), %d iterations, best %d, %lld moves, connectivity_w %lld -> "
                     "%lld, cut nets %lld, part weights %lld..%lld, over_bound %lld, %.3f s\n", o.jet_eps,
@@ -603,11 +642,12 @@ int run_kway_ml(const Opts& o) {
 
 constexpr const char* KD_USAGE =
     "Usage: gKL2 <input_file> -EIG --k <parts> --kway-direct <imbalance> [--ml-coarse <N>] [--jet-iters <I>] "
-    "[--contract-host] [--ml-weighted-laplacian] [--coarsen match|cluster]  (the direct k-way multilevel partition: one "
+    "[--contract-host] [--ml-weighted-laplacian] [--coarsen match|cluster] [--rebalance]  (the direct k-way multilevel partition: one "
     "coarsening, the Jet refinement at every level; needs --k with 2 <= parts <= 256 and an imbalance >= 0; excludes "
     "--kway-multilevel, --multilevel, --refine, --refine-weighted, --refine-jet, --sweep and --fm; --contract-host "
-    "contracts on the host; --coarsen cluster coarsens by multi-node clustering, match (the default) by matching; the file "
-    "is read as hMETIS reads it)\n";
+    "contracts on the host; --coarsen cluster coarsens by multi-node clustering, match (the default) by matching; "
+    "--rebalance rebalances a level that starts above the bound before its Jet refinement, and the rebalance: line "
+    "follows; the file is read as hMETIS reads it)\n";
 
 // gKL2 <in.hgr> -EIG --k N --kway-direct EPS: one summary line beginning "kway-direct:", results/<base>.part.<N>
 int run_kway_direct(const Opts& o) {
@@ -616,10 +656,18 @@ int run_kway_direct(const Opts& o) {
     const ek_solve_opts so = solve_opts(o);
     if (!ek::kway_direct_file_for_cli) throw Fail{"this build carries no direct k-way path"};
     ek_kway_direct_result r{};
+    ek_kway_direct_rb_result rb{};
     const int32_t flags = (o.kd_host ? EK_KWAY_DIRECT_HOST_CONTRACT : 0) | (o.ml_wlap ? EK_KWAY_DIRECT_WEIGHTED_LAPLACIAN : 0);
-    check(ek::kway_direct_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.kd_eps, o.ml_coarse, o.jet_iters,
-                                       flags, o.kd_cluster, &r),
-          "direct k-way partition");
+    if (o.rb) {
+        if (!ek::kway_direct_rb_file_for_cli) throw Fail{"this build carries no k-way rebalancing"};
+        check(ek::kway_direct_rb_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.kd_eps, o.ml_coarse,
+                                              o.jet_iters, flags, o.kd_cluster, &r, &rb),
+              "direct k-way partition with rebalancing");
+    } else {
+        check(ek::kway_direct_file_for_cli(ci.get(), o.input.c_str(), o.kway, &so.lanczos, o.kd_eps, o.ml_coarse,
+                                           o.jet_iters, flags, o.kd_cluster, &r),
+              "direct k-way partition");
+    }
     long long iters = 0, moves = 0;
     for (int l = 0; l <= r.levels; ++l) {
         iters += r.jet_iters[l];
@@ -636,6 +684,16 @@ int run_kway_direct(const Opts& o) {
                 (long long)r.conn_w_before[r.levels], (long long)r.soed, iters, moves, o.kd_host ? "host" : "device",
                 o.kd_cluster == EK_COARSEN_CLUSTER ? "cluster" : "match", r.t_total, r.t_match, r.t_contract, r.t_initial, r.t_jet, r.t_metrics, secs(t0),
                 base_name(o.input).c_str(), r.k, o.ml_wlap ? ", wlap=1" : "");
+    if (o.rb) {
+        long long levels = 0, rounds = 0, rmoves = 0;
+        for (int l = 0; l <= r.levels; ++l) {
+            levels += rb.over_before[l] > 0;
+            rounds += rb.rb_rounds[l];
+            rmoves += rb.rb_moves[l];
+        }
+        std::printf("rebalance: levels rebalanced %lld, %lld rounds, %lld moves, excess left %lld, %.3f s\n", levels,
+                    rounds, rmoves, (long long)rb.excess_after[0], rb.t_rebalance);
+    }
     return 0;
 }
 
@@ -725,6 +783,12 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
                 o.kd_eps = std::stod(need("--kway-direct"));
                 if (!std::isfinite(o.kd_eps) || o.kd_eps < 0) throw Fail{"--kway-direct takes an imbalance >= 0"};
             } else if (a == "--contract-host") o.kd_host = true;
+            else if (a == "--rebalance") o.rb = true;
+            else if (a == "--rebalance-to") {
+                o.rbt = true;  // (before the value, as --refine-weighted)
+                o.rbt_eps = std::stod(need("--rebalance-to"));
+                if (!std::isfinite(o.rbt_eps) || o.rbt_eps < 0) throw Fail{"--rebalance-to takes an imbalance >= 0"};
+            }
             else if (a == "--coarsen") {
                 o.kd_coarsen = true;  // (before the value, as --refine-weighted)
                 const std::string v = need("--coarsen");
@@ -749,7 +813,7 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             std::fprintf(stderr, "Error: %s\n", e.msg.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
             if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
-                a == "--jet-iters")
+                a == "--jet-iters" || a == "--rebalance-to")
                 std::printf("%s", ML_USAGE);
             if (a == "--kway-direct" || a == "--coarsen") std::printf("%s", KD_USAGE);
             return 1;
@@ -757,15 +821,16 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             std::fprintf(stderr, "Error: bad value for %s\n", a.c_str());
             if (a.rfind("--fm", 0) == 0) std::printf("%s", FM_USAGE);
             if (a.rfind("--m", 0) == 0 || a == "--kway-multilevel" || a == "--refine-weighted" || a == "--refine-jet" ||
-                a == "--jet-iters")
+                a == "--jet-iters" || a == "--rebalance-to")
                 std::printf("%s", ML_USAGE);
             if (a == "--kway-direct" || a == "--coarsen") std::printf("%s", KD_USAGE);
             return 1;
         }
     }
     try {
-        if (o.kd || o.kd_host || o.kd_coarsen) {  // the direct k-way path: refused with any other partitioner or refinement
-            if (!o.kd || o.kway < 2 || o.kway > 256 || o.ml || o.kml || o.refine || o.refine_w || o.jet || o.sweep ||
+        // the direct k-way path: refused with any other partitioner or refinement; --rebalance needs it
+        if (o.kd || o.kd_host || o.kd_coarsen || o.rb) {
+            if (!o.kd || o.rbt || o.kway < 2 || o.kway > 256 || o.ml || o.kml || o.refine || o.refine_w || o.jet || o.sweep ||
                 o.sweep_ratio || o.fm || o.fm_sub || o.weighted || o.sweep_weighted || o.no_kl || o.tool != "gKL2" ||
                 !(pos.size() == 2 && pos[1] == "-EIG")) {
                 std::printf("%s", KD_USAGE);
@@ -777,6 +842,10 @@ extern "C" int ek_cli_main_ex(const char* tool_c, int argc, char** argv, int fla
             return run_kway_direct(o);
         }
         if (o.refine_w && !o.kml) {  // --refine-weighted follows --kway-multilevel only
+            std::printf("%s", ML_USAGE);
+            return 1;
+        }
+        if (o.rbt && (!o.kml || o.refine_w)) {  // --rebalance-to follows --kway-multilevel only
             std::printf("%s", ML_USAGE);
             return 1;
         }

@@ -264,6 +264,12 @@ void refine_w_prepare(const char* who, const ek_hgr* h, const ek_kway_refine_opt
 ek_kway_jet_opts jet_prepare(const char* who, const ek_hgr* h, const ek_kway_jet_opts* opts, const int64_t* bounds,
                              const int32_t* part, RefineWInput& out);
 
+// kway_rebalance.cpp — what the host and the device rebalancing (§21) share:
+// the input, refine_w_prepare under k and the imbalance of the opts; returns
+// the opts with the defaults filled in
+ek_kway_rebalance_opts rebalance_prepare(const char* who, const ek_hgr* h, const ek_kway_rebalance_opts* opts,
+                                         const int64_t* bounds, const int32_t* part, RefineWInput& out);
+
 // match.cpp — what the host and the device matching share: the argument checks
 // (EK_EINVAL as eigkl.h lists it; the opts with the defaults filled in) and the
 // input, weights_prepare's
@@ -869,6 +875,22 @@ struct JetDev {
 // slot (device, zero before the iteration): the iteration's candidates,
 // passing candidates and accepted moves (slot[3] is left alone).  nets > 0.
 void jet_iteration(hipStream_t s, const JetDev& d, unsigned long long* slot);
+
+// kernels_rebalance.hip — the k-way rebalancing (ek_kway_rebalance, §21).
+// RefineWDev's arrays (win unused; list is list A, the proposers) and:
+struct RebalDev {
+    RefineWDev r;
+    unsigned long long* list_b;  // n: the evicted nodes' keys
+    unsigned long long* thr_a;   // 256: the source select's thresholds
+    long long* room;             // 256: x(a) - 1 for a in O, -1 elsewhere (rebal_excess)
+    const long long* zero;       // 256 zeros: the source select's "S"
+};
+// rec (device, 4 words): [0] the moves, [1] the proposers, [2] X, [3] the
+// evicted.  rebal_excess writes rec[2] and room from S and L; rebal_round
+// (rec[0], [1] and [3] zero before, room of the state at its start) runs a
+// round up to its moves and then rebal_excess.  nets >= 0.
+void rebal_excess(hipStream_t s, const RebalDev& d, unsigned long long* rec);
+void rebal_round(hipStream_t s, const RebalDev& d, unsigned long long* rec);
 
 // kernels_sweep.hip — the sweep cuts (ek_sweep_cut, ek_sweep_cut_w): sort,
 // scans, the count and the weighted profile, prefix weights, the two choices

@@ -29,8 +29,10 @@ void chk(int rc) {
 
 using Hgr = std::unique_ptr<ek_hgr, void (*)(ek_hgr*)>;
 
+// rb: null for ek_partition_kway_direct_ex; otherwise the rebalancing step of
+// ek_partition_kway_direct_rb before every level's Jet, and its record
 void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, int32_t coarsening, int32_t* part_out,
-               ek_kway_direct_result* result) {
+               ek_kway_direct_result* result, ek_kway_direct_rb_result* rb = nullptr) {
     const auto t0 = clk::now();
     ek_kway_direct_opts o;
     ek_kway_direct_default_opts(&o);
@@ -118,6 +120,12 @@ void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, in
     ek_kway_jet_opts jo = o.jet;
     jo.k = o.k;
     jo.imbalance = o.imbalance;
+    ek_kway_rebalance_opts bo;
+    ek_kway_rebalance_default_opts(&bo);
+    bo.k = o.k;
+    bo.imbalance = o.imbalance;
+    ek_kway_direct_rb_result br{};
+    std::vector<int64_t> pw(size_t(4 + o.k));
     for (int l = L; l >= 0; --l) {
         const ek_hgr* g = l ? level[size_t(l) - 1].get() : &h;
         if (l < L) {
@@ -125,6 +133,24 @@ void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, in
             std::vector<int32_t> fine(cl.size());
             for (size_t i = 0; i < cl.size(); ++i) fine[i] = part[size_t(cl[i])];
             part.swap(fine);
+        }
+        if (rb) {  // the level's weights; the rebalancer only if a part is above Lk
+            t = clk::now();
+            chk(ek_kway_metrics_w_host(g, part.data(), o.k, pw.data()));
+            for (int32_t p = 0; p < o.k; ++p)
+                if (pw[size_t(4 + p)] > r.part_bound) {
+                    ++br.over_before[l];
+                    br.excess_before[l] += pw[size_t(4 + p)] - r.part_bound;
+                }
+            br.excess_after[l] = br.excess_before[l];
+            if (br.over_before[l] > 0) {
+                ek_kway_rebalance_result rr{};
+                chk(ek_kway_rebalance(ctx, g, &bo, nullptr, part.data(), nullptr, 0, &rr));
+                br.rb_rounds[l] = rr.rounds;
+                br.rb_moves[l] = rr.moves;
+                br.excess_after[l] = rr.excess;
+            }
+            br.t_rebalance += since(t);
         }
         t = clk::now();
         ek_kway_jet_result jr{};
@@ -155,6 +181,7 @@ void partition(ek_ctx* ctx, const ek_hgr& h, const ek_kway_direct_opts* opts, in
     std::copy(part.begin(), part.end(), part_out);
     r.t_total = since(t0);
     if (result) *result = r;
+    if (rb) *rb = br;
 }
 
 }  // namespace
@@ -177,6 +204,25 @@ int kway_direct_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanc
     if (max_iters > 0) o.jet.max_iters = max_iters;
     if (lanczos) o.initial.ml.lanczos = *lanczos;
     return ek_partition_kway_direct_file_ex(ctx, path, &o, coarsening, nullptr, r);
+}
+
+// the same through ek_partition_kway_direct_rb_file, for `--kway-direct EPS --rebalance`
+int kway_direct_rb_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                                int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening,
+                                ek_kway_direct_result* r, ek_kway_direct_rb_result* rb);
+int kway_direct_rb_file_for_cli(ek_ctx* ctx, const char* path, int k, const ek_lanczos_opts* lanczos, double imbalance,
+                                int coarse_nodes, int max_iters, int32_t flags, int32_t coarsening,
+                                ek_kway_direct_result* r, ek_kway_direct_rb_result* rb) {
+    ek_kway_direct_opts o;
+    ek_kway_direct_default_opts(&o);
+    o.k = k;
+    o.imbalance = imbalance;
+    o.flags = flags;
+    o.write_results = 1;
+    if (coarse_nodes > 0) o.coarse_nodes = coarse_nodes;
+    if (max_iters > 0) o.jet.max_iters = max_iters;
+    if (lanczos) o.initial.ml.lanczos = *lanczos;
+    return ek_partition_kway_direct_rb_file(ctx, path, &o, coarsening, nullptr, r, rb);
 }
 }  // namespace ek
 
@@ -232,6 +278,42 @@ int ek_partition_kway_direct_file_ex(ek_ctx* ctx, const char* path, const ek_kwa
     partition(ctx, *h, opts, coarsening, part_out, &r);
     if (opts && opts->write_results) ek::write_part_file(path, opts->out_dir, r.k, h->nodes, part_out);
     if (result) *result = r;
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_partition_kway_direct_rb(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                int32_t* part_out, ek_kway_direct_result* result, ek_kway_direct_rb_result* rb) {
+    EK_TRY
+    if (!ctx || !h || (h->nodes > 0 && !part_out)) ek::fail(EK_EINVAL, "ek_partition_kway_direct_rb: null argument");
+    ek_kway_direct_rb_result br{};
+    partition(ctx, *h, opts, coarsening, part_out, result, &br);
+    if (rb) *rb = br;
+    return EK_OK;
+    EK_CATCH
+}
+
+int ek_partition_kway_direct_rb_file(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                     int32_t* part_out, ek_kway_direct_result* result, ek_kway_direct_rb_result* rb) {
+    EK_TRY
+    if (!ctx || !path) ek::fail(EK_EINVAL, "ek_partition_kway_direct_rb_file: null argument");
+    if (coarsening != EK_COARSEN_MATCH && coarsening != EK_COARSEN_CLUSTER)  // before the file is read
+        ek::fail(EK_EINVAL, "ek_partition_kway_direct_rb_file: coarsening %d (EK_COARSEN_MATCH or EK_COARSEN_CLUSTER)",
+                 int(coarsening));
+    ek_hgr* h = nullptr;
+    chk(ek_hgr_read_weighted(path, &h));
+    Hgr hg(h, ek_hgr_free);
+    std::vector<int32_t> own;
+    if (!part_out) {
+        own.resize(size_t(h->nodes));
+        part_out = own.data();
+    }
+    ek_kway_direct_result r{};
+    ek_kway_direct_rb_result br{};
+    partition(ctx, *h, opts, coarsening, part_out, &r, &br);
+    if (opts && opts->write_results) ek::write_part_file(path, opts->out_dir, r.k, h->nodes, part_out);
+    if (result) *result = r;
+    if (rb) *rb = br;
     return EK_OK;
     EK_CATCH
 }

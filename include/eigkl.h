@@ -1416,6 +1416,92 @@ int ek_partition_kway_direct_file_ex(ek_ctx* ctx, const char* path, const ek_kwa
                                      int32_t* part_out, ek_kway_direct_result* result);
 
 /* ------------------------------------------------------------------ */
+/* k-way rebalancing: bring overweight parts under their bounds (DESIGN.md */
+/* §21, the second half of the Jet rule).  No reference counterpart.       */
+/* ------------------------------------------------------------------ */
+/* Input, weights, S(p) and the bounds L_p exactly as ek_kway_refine_w.  O =
+ * {p : S(p) > L_p}, the excess x(p) = max(0, S(p) - L_p), X = sum x(p).  With O
+ * empty the call returns the start (0 rounds).  Everything is integer, ties are
+ * broken by ids, and round i = 1, 2, ... reads only the state at its start:
+ *  (a) v proposes iff a = part(v) is in O and w(v) > 0 (nodes on no net too:
+ *      every g is 0).  g(v,b) = (r - D) + c(v,b) as ek_kway_refine_w's (a); the
+ *      target t(v) is the part b != a with S(b) + w(v) <= L_b of greatest g,
+ *      ties to the smaller b, whatever the sign of g (no part of O fits).  v is
+ *      a proposer iff such a part exists; K(v) = ((g + 2^31) << 32) | ~id;
+ *  (b) per a in O the proposers of a in K-descending order: E(a) is the
+ *      shortest prefix whose summed w reaches x(a), all of them when their
+ *      total stays below it;
+ *  (c) per part b the nodes of the union of the E(a) with target b in
+ *      K-descending order: the accepted set is the longest prefix whose summed
+ *      w is at most L_b - S(b), ek_kway_refine_w's (c);
+ *  (d) accepted nodes move; evicted nodes that were not accepted stay and
+ *      propose again against the new S;
+ *  (e) stop when O is empty after the round, when a round accepted nothing
+ *      (that round is neither counted nor logged), or after max_rounds rounds
+ *      (when > 0).
+ * Every logged round lowers X by at least 1; a part at or below its bound never
+ * ends above it; a part above its bound never receives.  A part still above
+ * its bound at the end (parts_over_bound, not an error) has no node of
+ * positive weight that fits any other part, unless max_rounds stopped the run.
+ * There is no promise about the weighted connectivity: it may rise, and the
+ * result carries both values, recounted from the start and the final state. */
+typedef struct {
+    int32_t k;          /* number of parts, 2..256 */
+    int32_t max_rounds; /* <= 0: none */
+    double imbalance;   /* epsilon >= 0 of the uniform bound; default 0.03; ignored with bounds */
+} ek_kway_rebalance_opts;
+void ek_kway_rebalance_default_opts(ek_kway_rebalance_opts* opts);
+
+typedef struct {
+    int32_t k, rounds;                          /* rounds that moved a node */
+    int64_t moves;                              /* accepted moves over all rounds */
+    int64_t total_weight;                       /* W */
+    int64_t bound_min, bound_max;               /* least / greatest L_p as used */
+    int64_t parts_over_before, parts_over_bound; /* |O| of the start / of the result */
+    int64_t excess_before, excess;              /* X of the start / of the result */
+    int64_t connectivity_w_before;              /* of the start */
+    int64_t connectivity_w;                     /* of the result; may exceed the start's */
+    int64_t cut_nets, connectivity, soed;       /* ek_kway_metrics_w of the result */
+    int64_t part_w_min, part_w_max;             /* of the result */
+    double t_setup, t_rounds, t_metrics;        /* wall seconds (host clock) */
+} ek_kway_rebalance_result;
+
+/* The rebalancing on the host (no GPU): the checker of ek_kway_rebalance,
+ * single threaded and written from the rule.  part_inout: the start on entry,
+ * the final state on return.  round_log (may be NULL) gets four values per
+ * logged round, for the first log_rounds rounds: proposers, evicted nodes,
+ * moved nodes and X after the round.  EK_EINVAL as ek_kway_refine_w_host. */
+int ek_kway_rebalance_host(const ek_hgr* h, const ek_kway_rebalance_opts* opts, const int64_t* bounds /* k, or NULL */,
+                           int32_t* part_inout, int64_t* round_log, int64_t log_rounds,
+                           ek_kway_rebalance_result* result);
+/* The same on the GPU: the same part vector, round log and result integers.
+ * Eight launches a round; the host reads one 32-byte record per round.
+ * EK_ESTATE on a multi-rank context; EK_EHIP if the rounds pass the excess of
+ * the start (every round lowers X) or the weights kept differ from a recount.
+ * Keeps nothing on the context: every buffer is local to the call. */
+int ek_kway_rebalance(ek_ctx* ctx, const ek_hgr* h, const ek_kway_rebalance_opts* opts, const int64_t* bounds,
+                      int32_t* part_inout, int64_t* round_log, int64_t log_rounds, ek_kway_rebalance_result* result);
+
+/* ek_partition_kway_direct_ex with a rebalancing step: at every level, after
+ * the initial partition or the projection and before ek_kway_jet, if any part
+ * is above Lk, ek_kway_rebalance under the uniform bound.  Level l of the
+ * arrays is H_l: the parts above Lk and (excess_before) their excess when the
+ * level was reached, the rebalancer's rounds and moves, the excess it left.
+ * When no level starts above its bound, part_out and every integer of result
+ * equal ek_partition_kway_direct_ex's.  rb may be NULL. */
+typedef struct {
+    int64_t over_before[EK_ML_LEVELS + 1], excess_before[EK_ML_LEVELS + 1];
+    int64_t rb_rounds[EK_ML_LEVELS + 1], rb_moves[EK_ML_LEVELS + 1];
+    int64_t excess_after[EK_ML_LEVELS + 1];
+    double t_rebalance; /* wall seconds (host clock), inside result's t_total */
+} ek_kway_direct_rb_result;
+int ek_partition_kway_direct_rb(ek_ctx* ctx, const ek_hgr* h, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                int32_t* part_out /* nodes */, ek_kway_direct_result* result,
+                                ek_kway_direct_rb_result* rb);
+int ek_partition_kway_direct_rb_file(ek_ctx* ctx, const char* path, const ek_kway_direct_opts* opts, int32_t coarsening,
+                                     int32_t* part_out, ek_kway_direct_result* result, ek_kway_direct_rb_result* rb);
+
+/* ------------------------------------------------------------------ */
 /* Drop-in CLIs: argv exactly as cEIG.cpp:138-237 / cKL.cpp:424-468 /    */
 /* gKL.cu:672-713 / gKL2.cu:989-1033, outputs relative to the CWD.       */
 /* tool = "cEIG" | "cKL" | "gKL" | "gKL2".  Returns the process exit code. */
